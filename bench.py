@@ -20,10 +20,14 @@ device batch gather, fused LSTM forward, fused cross-entropy, fused BPTT
 backward, native RCCL all-reduce, fused Adam.  ``--warmup`` untimed steps
 first; the timed region is bracketed by a barrier + device synchronize on both
 sides; the MAX elapsed time over ranks is reported by rank 0 as ONE JSON line.
-``step_seq_per_s`` is a second, full-batch-only measurement (the per-step
-figure of earlier rounds).
+A plain run does only that.  ``--full`` adds ``step_seq_per_s``, a second,
+full-batch-only measurement (the per-step figure of earlier rounds), in a
+timed run of its own.  ``--dump-outputs DIR`` writes what the last timed step
+returned and the parameters it left behind as ``DIR/<name>.npy`` (float32), so
+that two builds can be compared output for output.
 
     python bench.py                       # 1 GPU
+    python bench.py --full                # ... and the secondary measurement
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \\
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8
 """
@@ -44,6 +48,8 @@ METRIC = "sequences/sec (whole node) for motion RNN DDP at 1/2/4/8 MI355X; epoch
 # Reference DDP (MPI) seq/s at global batch 1440, 1/2/4/8 nodes (dedup table)
 BASELINE_SEQ_PER_S = {1: 44.8, 2: 85.9, 4: 128.5, 8: 213.3}
 EPOCH_SEQUENCES = 6912
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 20240607
 
 
 def parse(argv=None):
@@ -67,7 +73,38 @@ def parse(argv=None):
                     help="replay the synced step (fwd/BPTT, RCCL all-reduce, Adam) from a HIP graph")
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32",
                     help="bf16: BASELINE config 2 (bf16 inputs/weights, fp32 accumulate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary full-batch-only measurement (step_seq_per_s, step_ms_full_batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (its [loss, n, correct] "
+                         "statistics) and left behind (every model parameter) as DIR/<name>.npy (rank 0)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(directory: str, stats, model) -> None:
+    """The timed path's results after its last step, one float32 .npy each:
+    ``stats`` = that step's [loss, batch size, correct] (what
+    ``Trainer.train_batch`` returns) and ``param.<name>`` = every parameter of
+    the model the step updated in place.  With the same arguments the data,
+    the initial weights and the batch order are the same from run to run.
+    At most DUMP_MAX_BYTES in all: of a model larger than that (--hidden in
+    the thousands) every array beyond an equal share keeps a fixed, seeded
+    sample of its elements (sorted flat indices, the same from run to run)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"stats": stats}
+    for name, p in model.state_dict().items():
+        arrays["param." + name] = p
+    share = None
+    if sum(t.numel() for t in arrays.values()) * 4 > DUMP_MAX_BYTES:
+        share = DUMP_MAX_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        if share is not None and a.size > share:
+            pick = np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=share, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _max_over_ranks(x: float, dev) -> float:
@@ -200,20 +237,25 @@ def main(argv=None):
     epochs = args.steps / steps_per_epoch
     global_batch = per_rank * world
     base = BASELINE_SEQ_PER_S.get(world)
-    # secondary: full-batch step throughput (the short last batch skipped),
-    # the per-step figure of earlier rounds
-    full = []
-    stream = epoch_batches(2000)
-    while len(full) < args.steps + 3:
-        b = next(stream)
-        if b.numel() == per_rank:
-            full.append(b)
-    for b in full[:3]:  # per-step graph capture of the synced step (N > 1) outside the clock
-        trainer.train_batch(loader.make_batch(b))
-    step_elapsed, _ = timed_run(full[3:], per_step=True)
-    step_value = per_rank * world * args.steps / step_elapsed
-    # sanity: loss must be finite after training
+    # sanity: loss must be finite after training (read before any later step
+    # reuses the row of the statistics ring that ``stats`` is a view of)
     loss = float(stats[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats, model)
+    step_elapsed = step_value = None
+    if args.full:
+        # secondary: full-batch step throughput (the short last batch skipped),
+        # the per-step figure of earlier rounds
+        full = []
+        stream = epoch_batches(2000)
+        while len(full) < args.steps + 3:
+            b = next(stream)
+            if b.numel() == per_rank:
+                full.append(b)
+        for b in full[:3]:  # per-step graph capture of the synced step (N > 1) outside the clock
+            trainer.train_batch(loader.make_batch(b))
+        step_elapsed, _ = timed_run(full[3:], per_step=True)
+        step_value = per_rank * world * args.steps / step_elapsed
     if rank == 0:
         out = {
             "metric": METRIC,
@@ -241,11 +283,12 @@ def main(argv=None):
             "epoch_time_s": round(elapsed / epochs, 6),
             "epoch_sequences": n_train,
             "timed_sequences": seqs,
-            "step_seq_per_s": round(step_value, 2),
-            "step_ms_full_batch": round(step_elapsed / args.steps * 1e3, 4),
             "final_loss": round(loss, 6),
             "baseline_seq_per_s": base,
         }
+        if args.full:
+            out["step_seq_per_s"] = round(step_value, 2)
+            out["step_ms_full_batch"] = round(step_elapsed / args.steps * 1e3, 4)
         print(json.dumps(out), flush=True)
     env.shutdown()
 

@@ -11,10 +11,28 @@ from typing import Dict, List, Optional
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def free_port() -> int:
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def free_port(span: int = 1) -> int:
+    """A port P with P .. P + span - 1 all free right now.  The parameter
+    server derives its other listeners from the master port (P + 1: payload
+    group, P + 2: payload-mode store), so its tests ask for the whole range:
+    a neighbour in use by another process makes rank 0 fail with EADDRINUSE
+    and the other ranks wait for it until their timeout."""
+    for _ in range(200):
+        socks = [socket.socket() for _ in range(span)]
+        try:
+            socks[0].bind(("127.0.0.1", 0))
+            port = socks[0].getsockname()[1]
+            if port + span > 65536:
+                continue
+            for k in range(1, span):
+                socks[k].bind(("127.0.0.1", port + k))
+            return port
+        except OSError:
+            continue
+        finally:
+            for s in socks:
+                s.close()
+    raise RuntimeError(f"no {span} consecutive free ports found")
 
 
 def cpu_env(extra: Optional[Dict[str, str]] = None) -> Dict[str, str]:

@@ -6,6 +6,9 @@ import sys
 from _mp import ROOT, run
 
 sys.path.insert(0, os.path.join(ROOT, "bench"))
+# the reference's published result files, stderr / stdout cut down to the
+# lines the report parses (tests/golden/README.md)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_results")
 import report  # noqa: E402
 import runner  # noqa: E402
 
@@ -33,11 +36,7 @@ def test_runner_resume_and_report(tmp_path):
 
 
 def test_report_reproduces_baseline_table():
-    ev = "/root/reference/evaluation"
-    files = [os.path.join(ev, f) for f in ("results_202007141530.json", "results_202007141730.json")]
-    if not all(os.path.exists(f) for f in files):
-        import pytest
-        pytest.skip("reference result files not mounted")
+    files = [os.path.join(GOLDEN, f) for f in ("results_202007141530.json", "results_202007141730.json")]
     rows = report.aggregate(files)
     # BASELINE.md dedup table: DDP bs1440 44.8 / 85.9 / 128.5 / 213.3 seq/s
     got = [round(rows[("distributed", n, 1440)]["seq_per_s"], 1) for n in (1, 2, 4, 8)]
@@ -48,11 +47,7 @@ def test_report_reproduces_baseline_network_rows(tmp_path):
     """the network notebook's numbers (BASELINE.md 'Other
     recorded numbers') from the reference's netem result files, and the
     figures written."""
-    import pytest
-    ev = "/root/reference/evaluation"
-    files = [os.path.join(ev, f) for f in ("results_network_202007211500.json", "results_network_202007211630.json")]
-    if not all(os.path.exists(f) for f in files):
-        pytest.skip("reference result files not mounted")
+    files = [os.path.join(GOLDEN, f) for f in ("results_network_202007211500.json", "results_network_202007211630.json")]
     rows = report.aggregate_network(files)
 
     def row(tr, rt, vals):

@@ -44,7 +44,7 @@ def test_mpirun_style_rank_discovery(tmp_path):
 
 
 def test_parameter_server_liveness(tmp_path):
-    port = str(free_port())
+    port = str(free_port(3))  # + the payload group's and the payload-mode store's
     common = ["--seed", "1", "--epochs", "1", "--batch-size", "96", "--no-validation", "--synthetic",
               "--synthetic-size", "192", "--device", "cpu", "--hidden-units", "8", "parameter-server",
               "--world-size", "3", "--master-address", "127.0.0.1", "--master-port", port]
@@ -70,7 +70,7 @@ def test_parameter_server_collective_payloads(tmp_path):
     """RPC as control plane, batch/logits/logit-gradient over {server, trainer}
     send/recv groups (gloo here; RCCL when every rank owns a GPU): both
     trainers step the server's model and its loss goes down."""
-    port = str(free_port())
+    port = str(free_port(3))  # + the payload group's and the payload-mode store's
     common = ["--seed", "1", "--epochs", "4", "--batch-size", "96", "--no-validation", "--synthetic",
               "--synthetic-size", "384", "--device", "cpu", "--hidden-units", "8", "--log-interval", "1",
               "parameter-server", "--world-size", "3", "--master-address", "127.0.0.1", "--master-port", port,
