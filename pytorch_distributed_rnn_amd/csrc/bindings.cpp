@@ -234,8 +234,45 @@ void check_stack(const std::vector<Tensor>& w, int64_t NL, int64_t H, int64_t I,
   }
 }
 
-// Returns {out_or_hseq, hn, cn, act}.  x: [B,T,I] (batch_first) or [T,B,I];
-// with idx, x is a [N,T,I] source table and B = len(idx).
+// The small-H argument structs (forward / backward / dW) share field names:
+// the three fillers below are templated on the struct.
+// Input geometry.  x: [B,T,I] (batch_first) or [T,B,I]; with idx, x is a
+// [N,T,I] source table and B = len(idx).
+template <class Args>
+void set_input(Args& a, const Tensor& x, const optional<Tensor>& idx, bool batch_first) {
+  const bool gathered = idx.has_value() && idx->defined();
+  const int bd = (gathered || batch_first) ? 0 : 1;  // batch dimension of x
+  a.x = reinterpret_cast<const float*>(x.data_ptr());
+  a.x_bf16 = x.scalar_type() == at::kBFloat16;
+  a.idx = gathered ? idx->data_ptr<int64_t>() : nullptr;
+  a.x_sb = x.stride(bd); a.x_st = x.stride(1 - bd);
+  a.B = (int)(gathered ? idx->size(0) : x.size(bd)); a.T = (int)x.size(1 - bd); a.I = (int)x.size(2);
+}
+
+// Per-layer weight pointers (the forward also takes the biases).
+template <class Args>
+void set_weights(Args& a, const std::vector<Tensor>& w, int64_t NL) {
+  for (int64_t l = 0; l < NL; ++l) {
+    a.w_ih[l] = w[l * 4 + 0].data_ptr<float>();
+    a.w_hh[l] = w[l * 4 + 1].data_ptr<float>();
+    if constexpr (std::is_same_v<Args, PdrnnLstmSmallFwdArgs>) {
+      a.b_ih[l] = w[l * 4 + 2].defined() ? w[l * 4 + 2].data_ptr<float>() : nullptr;
+      a.b_hh[l] = w[l * 4 + 3].defined() ? w[l * 4 + 3].data_ptr<float>() : nullptr;
+    }
+  }
+}
+
+// Per-layer offsets of the parameter gradients in a slab row.
+template <class Args>
+void set_offsets(Args& a, const StackLayout& L, int64_t NL) {
+  for (int64_t l = 0; l < NL; ++l) {
+    a.off_wih[l] = L.off_wih[l]; a.off_whh[l] = L.off_whh[l];
+    a.off_bih[l] = L.off_bih[l]; a.off_bhh[l] = L.off_bhh[l];
+  }
+  a.P = L.P;
+}
+
+// Returns {out_or_hseq, hn, cn, act}.
 std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx, const std::vector<Tensor>& w,
                                    const optional<Tensor>& h0, const optional<Tensor>& c0, int64_t H, int64_t NL,
                                    bool batch_first, bool save, bool need_out, int64_t nb, int64_t split,
@@ -248,31 +285,18 @@ std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx,
   const int64_t I = x.size(2);
   bool has_bias = false;
   check_stack(w, NL, H, I, has_bias);
-  int64_t B, T, x_sb, x_st;
   if (idx.has_value() && idx->defined()) {
     TORCH_CHECK(batch_first, "gathered input requires batch_first");
     TORCH_CHECK(idx->scalar_type() == at::kLong && idx->is_contiguous());
-    B = idx->size(0); T = x.size(1); x_sb = x.stride(0); x_st = x.stride(1);
-  } else if (batch_first) {
-    B = x.size(0); T = x.size(1); x_sb = x.stride(0); x_st = x.stride(1);
-  } else {
-    T = x.size(0); B = x.size(1); x_sb = x.stride(1); x_st = x.stride(0);
   }
+  PdrnnLstmSmallFwdArgs a{};
+  a.prio = prio_env();
+  set_input(a, x, idx, batch_first);
+  set_weights(a, w, NL);
+  const int64_t B = a.B, T = a.T;
   auto opts = x.options().dtype(at::kFloat);
   Tensor hn = at::empty({NL, B, H}, opts), cn = at::empty({NL, B, H}, opts);
   Tensor hseq, act, out;
-  PdrnnLstmSmallFwdArgs a{};
-  a.prio = prio_env();
-  a.x = reinterpret_cast<const float*>(x.data_ptr());
-  a.x_bf16 = x.scalar_type() == at::kBFloat16;
-  a.idx = (idx.has_value() && idx->defined()) ? idx->data_ptr<int64_t>() : nullptr;
-  a.x_sb = x_sb; a.x_st = x_st;
-  for (int64_t l = 0; l < NL; ++l) {
-    a.w_ih[l] = w[l * 4 + 0].data_ptr<float>();
-    a.w_hh[l] = w[l * 4 + 1].data_ptr<float>();
-    a.b_ih[l] = has_bias ? w[l * 4 + 2].data_ptr<float>() : nullptr;
-    a.b_hh[l] = has_bias ? w[l * 4 + 3].data_ptr<float>() : nullptr;
-  }
   if (h0.has_value() && h0->defined()) TORCH_CHECK(h0->is_contiguous() && h0->numel() == NL * B * H, "h0 shape");
   if (c0.has_value() && c0->defined()) TORCH_CHECK(c0->is_contiguous() && c0->numel() == NL * B * H, "c0 shape");
   a.h0 = opt_ptr(h0); a.c0 = opt_ptr(c0);
@@ -289,7 +313,7 @@ std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx,
     a.o_st = batch_first ? H : B * H;
   }
   a.hn = hn.data_ptr<float>(); a.cn = cn.data_ptr<float>();
-  a.B = (int)B; a.T = (int)T; a.I = (int)I; a.NL = (int)NL; a.cell = (int)cell;
+  a.NL = (int)NL; a.cell = (int)cell;
   if (split <= 0) split = pdrnn_lstm_small_max_split((int)H, (int)NL, 0);
   Tensor stamps;
   if (stamps_enabled()) {
@@ -315,34 +339,20 @@ std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx,
   bool has_bias = false;
   check_stack(w, NL, H, I, has_bias);
   const bool gathered = idx.has_value() && idx->defined();
-  int64_t B, T, x_sb, x_st;
-  if (gathered) {
-    B = idx->size(0); T = x.size(1); x_sb = x.stride(0); x_st = x.stride(1);
-  } else if (batch_first) {
-    B = x.size(0); T = x.size(1); x_sb = x.stride(0); x_st = x.stride(1);
-  } else {
-    T = x.size(0); B = x.size(1); x_sb = x.stride(1); x_st = x.stride(0);
-  }
   TORCH_CHECK(hseq.is_contiguous() && act.is_contiguous());
   StackLayout L = stack_layout(w, NL, has_bias);
+  PdrnnLstmSmallBwdArgs a{};
+  a.prio = prio_env();
+  set_input(a, x, idx, batch_first);
+  set_weights(a, w, NL);
+  set_offsets(a, L, NL);
+  const int64_t B = a.B, T = a.T;
   auto opts = x.options().dtype(at::kFloat);
   if (split <= 0) split = pdrnn_lstm_small_max_split((int)H, (int)NL, 1);
   const int grid = pdrnn_lstm_small_bwd_grid((int)H, (int)NL, (int)T, (int)B, (int)nb, (int)split);
   TORCH_CHECK(grid > 0, "unsupported backward tile nb=", nb);
   Tensor slab = at::empty({std::max(grid, 1), L.P}, opts);
   Tensor dx, dh0, dc0;
-  PdrnnLstmSmallBwdArgs a{};
-  a.prio = prio_env();
-  a.x = reinterpret_cast<const float*>(x.data_ptr());
-  a.x_bf16 = x.scalar_type() == at::kBFloat16;
-  a.idx = gathered ? idx->data_ptr<int64_t>() : nullptr;
-  a.x_sb = x_sb; a.x_st = x_st;
-  for (int64_t l = 0; l < NL; ++l) {
-    a.w_ih[l] = w[l * 4 + 0].data_ptr<float>();
-    a.w_hh[l] = w[l * 4 + 1].data_ptr<float>();
-    a.off_wih[l] = L.off_wih[l]; a.off_whh[l] = L.off_whh[l];
-    a.off_bih[l] = L.off_bih[l]; a.off_bhh[l] = L.off_bhh[l];
-  }
   a.h0 = opt_ptr(h0); a.c0 = opt_ptr(c0);
   a.hseq = hseq.data_ptr<float>(); a.act = act.data_ptr<float>();
   if (dout.has_value() && dout->defined()) {
@@ -368,8 +378,7 @@ std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx,
     a.dh0 = dh0.data_ptr<float>(); a.dc0 = dc0.data_ptr<float>();
   }
   a.slab = slab.data_ptr<float>();
-  a.P = L.P;
-  a.B = (int)B; a.T = (int)T; a.I = (int)I; a.NL = (int)NL; a.cell = (int)cell;
+  a.NL = (int)NL; a.cell = (int)cell;
   Tensor dparams;
   float beta = 0.f;
   if (grad_accum.has_value() && grad_accum->defined()) {
@@ -423,6 +432,93 @@ void report_phase_stamps(const Tensor& st) {
     }
     fprintf(stderr, " | total %.0f\n", tot);
   }
+}
+
+// Every path decision of the fused motion training step, as plain data: the
+// step (lstm_head_train_step) runs on it and Python can ask for it
+// (lstm_head_step_plan; the lstm_small_step_* queries ask about the gate-split
+// / K-split family alone).
+struct HeadStepShape {
+  int H, I, NL, T, B, cell;
+  int nb_fwd, split_fwd, nb_bwd, split_bwd;  // <= 0: the default
+  // the step's environment switches: sequence-in-wave kernels allowed, their
+  // one-launch step allowed, PDRNN_LSTM_STAMPS
+  bool sw_on = sw_enabled(), sw_one_launch = sw_one_launch_enabled(), stamps = stamps_enabled();
+};
+struct HeadStepPlan {
+  const char* error = nullptr;  // set: the shape / launch config is not served
+  // sw_one_launch / sw_two_launch (sequence-in-wave, forward + BPTT in one / two launches),
+  // one_launch (gate-split step kernel), deferred_dw (matrix-core dW launch) or register_dw
+  const char* path = "";
+  int nb_fwd = 1, split_fwd = 0, nb_bwd = 1, split_bwd = 0;  // resolved launch config
+  bool sw = false, sw_step = false, sw_rdw = false, one_launch = false, dwout = false, phase = false;
+  int sw_fmode = -1, sw_bmode = -1, sw_fnb = 1, sw_bnb = 1;
+  int gridb = 0, nb_dw = 1, grid_dw = 0, slab_rows = 0, stamp_rows_f = 0;  // (backward stamp rows = grid_dw)
+};
+
+HeadStepPlan plan_head_step(const HeadStepShape& s) {
+  HeadStepPlan p;
+  auto fail = [&](const char* why) { p.error = why; return p; };
+  const int H = s.H, I = s.I, NL = s.NL, T = s.T, B = s.B, cell = s.cell;
+  p.split_fwd = cell == 1 ? 1 : s.split_fwd > 0 ? s.split_fwd : pdrnn_lstm_small_max_split(H, NL, 0);  // GRU: gate-split only
+  p.split_bwd = s.split_bwd > 0 ? s.split_bwd : pdrnn_lstm_small_max_split(H, NL, 1);
+  if ((p.split_fwd != 1 && p.split_fwd != 2) || p.split_bwd != 1)
+    return fail("fused train step runs on the gate-split or 2-lane K-split forward and the unit-group backward");
+  p.nb_fwd = s.nb_fwd > 0 ? s.nb_fwd : 1;
+  p.nb_bwd = (s.nb_bwd > 0 && cell != 1) ? s.nb_bwd : 1;  // the GRU backward is single-sequence
+  p.gridb = pdrnn_lstm_small_bwd_grid(H, NL, T, B, p.nb_bwd, p.split_bwd);
+  if (p.gridb <= 0) return fail("fused train step: unsupported backward tile (nb_bwd)");
+  // Sequence-in-wave kernels (lstm_sw.hip: a sequence's recurrence never
+  // leaves its wave) for the motion shape; PDRNN_SW=0 keeps the gate-split /
+  // K-split family (A/B).  Weight gradients deferred to lstm_small_dw.
+  // (their act / hseq byte offsets are 32-bit buffer offsets under one
+  // 2 GiB descriptor: larger batches take the per-sequence-rebased family)
+  const int dw_mode = pdrnn_lstm_small_dwout_ok(H, NL, T);
+  p.sw = s.sw_on && pdrnn_lstm_sw_ok(H, I, NL, cell) == 1 && dw_mode != 0 && T <= 640 &&
+         pdrnn_lstm_sw_fits(NL, B, T) == 1;
+  if (p.sw) {
+    p.sw_fmode = pdrnn_lstm_sw_mode(NL, B, 0);
+    p.sw_bmode = pdrnn_lstm_sw_mode(NL, B, 1);
+    if (p.sw_bmode == 4 && T % 4) p.sw_bmode = 2;  // register dW: whole 4-step K steps
+    // sequences per workgroup: two in modes 1 / 3 (mode 5, the four-wave forward, runs one)
+    p.sw_fnb = pdrnn_lstm_sw_nb(p.sw_fmode);
+    p.sw_bnb = pdrnn_lstm_sw_nb(p.sw_bmode);
+  }
+  // latency regime (forward mode 5, backward mode 4): one launch for forward +
+  // BPTT (lstm_sw_step_kernel); mode 4: the BPTT waves form dW on the matrix
+  // cores, one slab row per sequence, no dW launch
+  p.sw_step = p.sw && p.sw_fmode == 5 && p.sw_bmode == 4 && !s.stamps && s.sw_one_launch &&
+              pdrnn_lstm_sw_step_ok(NL, B, T) == 1;
+  p.sw_rdw = p.sw && p.sw_bmode == 4;
+  // Above one residency round the BPTT defers its weight gradients: the
+  // recurrence writes the gate gradients (into `act`, in place) and the
+  // matrix-core kernel lstm_small_dw forms dW / db over all B*T rows, one slab
+  // row per K chunk (see pdrnn_lstm_small_bwd_dwout).  One round or less keeps
+  // the one-launch step (one sequence per workgroup in both passes: forward,
+  // head/CE and BPTT in one launch, register-resident dW).
+  p.dwout = p.sw || (p.nb_bwd == 1 && p.split_bwd == 1 && ((p.gridb < B && dw_mode == 1) || dw_mode == 2));
+  p.one_launch = !p.dwout && !s.stamps &&
+                 pdrnn_lstm_small_step_ok(H, NL, B, p.nb_fwd, p.split_fwd, p.nb_bwd, p.split_bwd, p.gridb) == 1;
+  p.nb_dw = p.dwout ? pdrnn_lstm_small_bwd_dwout_nb(H, NL, T, B) : p.nb_bwd;
+  p.grid_dw = !p.dwout ? p.gridb
+              : p.sw   ? (B + p.sw_bnb - 1) / p.sw_bnb
+                       : pdrnn_lstm_small_bwd_dwout_grid(H, NL, T, B, p.nb_dw);
+  if (p.grid_dw <= 0) return fail("deferred-dW backward: no resident grid");
+  p.slab_rows = p.sw_rdw ? B : p.dwout ? pdrnn_lstm_small_dw_chunks(H, NL, B, T) : p.gridb;
+  // PDRNN_TUNE sw_phase=1 (with PDRNN_LSTM_STAMPS): the phase-stamped build
+  // of the four-wave forward, stamp rows of 24 (report_phase_stamps)
+  p.phase = s.stamps && p.sw && p.sw_fmode == 5 && cell == 0 && pdrnn_tune_int("sw_phase", 0) != 0;
+  p.stamp_rows_f = p.sw ? (B + p.sw_fnb - 1) / p.sw_fnb : (B + p.nb_fwd - 1) / p.nb_fwd;
+  p.path = p.sw_step ? "sw_one_launch" : p.sw ? "sw_two_launch" : p.one_launch ? "one_launch"
+           : p.dwout ? "deferred_dw" : "register_dw";
+  return p;
+}
+
+// The same question put to the gate-split / K-split family alone.
+HeadStepPlan plan_small_family(int64_t H, int64_t NL, int64_t T, int64_t B, int64_t nb_fwd, int64_t split_fwd,
+                               int64_t nb_bwd, int64_t split_bwd) {
+  return plan_head_step({(int)H, (int)H, (int)NL, (int)T, (int)B, 0, (int)nb_fwd, (int)split_fwd, (int)nb_bwd,
+                         (int)split_bwd, false, false, false});
 }
 
 // Fused motion training step on the native path: LSTM stack forward with the
@@ -480,6 +576,14 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
   }
   const int64_t P_head = P_params - P_rnn;    // head weight (+ bias)
   const int64_t PH = P_head + 3;              // + [loss, count, correct]
+
+  // ---- plan: which kernels run, on which grids
+  const HeadStepPlan p = plan_head_step({(int)H, (int)I, (int)NL, (int)T, (int)B, (int)cell, (int)nb_fwd, (int)split_fwd,
+                                         (int)nb_bwd, (int)split_bwd});
+  TORCH_CHECK(!p.error, p.error, " (H=", H, ", layers=", NL, ", nb_bwd=", nb_bwd, ")");
+  const bool sw = p.sw, dwout = p.dwout;
+
+  // ---- allocate
   auto opts = x.options().dtype(at::kFloat);
   // hseq / act with the deferred-dW kernel's padding (one h row in front,
   // PDRNN_DW_PAD_ROWS rows behind: it streams whole stages without clamps)
@@ -488,59 +592,23 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
   Tensor act = at::empty({NL * B * T * 5 * H + PADR * 5 * H}, opts);
   Tensor hn = at::empty({NL, B, H}, opts), cn = at::empty({NL, B, H}, opts);
   Tensor dh_top = at::empty({B, H}, opts);
-  if (split_fwd <= 0) split_fwd = pdrnn_lstm_small_max_split((int)H, (int)NL, 0);
-  if (split_bwd <= 0) split_bwd = pdrnn_lstm_small_max_split((int)H, (int)NL, 1);
-  if (cell == 1) split_fwd = 1;  // GRU: gate-split forward only
-  TORCH_CHECK((split_fwd == 1 || split_fwd == 2) && split_bwd == 1,
-              "fused train step runs on the gate-split or 2-lane K-split forward and the unit-group backward");
-  if (nb_fwd <= 0) nb_fwd = 1;
-  if (nb_bwd <= 0 || cell == 1) nb_bwd = 1;  // the GRU backward is single-sequence
-  const int gridb = pdrnn_lstm_small_bwd_grid((int)H, (int)NL, (int)T, (int)B, (int)nb_bwd, (int)split_bwd);
-  TORCH_CHECK(gridb > 0, "unsupported backward tile nb=", nb_bwd);
-  // Sequence-in-wave kernels (lstm_sw.hip: a sequence's recurrence never
-  // leaves its wave) for the motion shape; PDRNN_SW=0 keeps the gate-split /
-  // K-split family below (A/B).  Weight gradients deferred to lstm_small_dw.
-  // (their act / hseq byte offsets are 32-bit buffer offsets under one
-  // 2 GiB descriptor: larger batches take the per-sequence-rebased family)
-  const bool sw = sw_enabled() && pdrnn_lstm_sw_ok((int)H, (int)I, (int)NL, (int)cell) == 1 &&
-                  pdrnn_lstm_small_dwout_ok((int)H, (int)NL, (int)T) != 0 && T <= 640 &&
-                  pdrnn_lstm_sw_fits((int)NL, (int)B, (int)T) == 1;
-  const int sw_fmode = sw ? pdrnn_lstm_sw_mode((int)NL, (int)B, 0) : -1;
-  int sw_bmode = sw ? pdrnn_lstm_sw_mode((int)NL, (int)B, 1) : -1;
-  if (sw_bmode == 4 && T % 4) sw_bmode = 2;  // register dW: whole 4-step K steps
-  // sequence-in-wave latency regime (forward mode 5, backward mode 4): one
-  // launch for forward + BPTT per step (lstm_sw_step_kernel)
-  const bool sw_step = sw && sw_fmode == 5 && sw_bmode == 4 && !stamps_enabled() && sw_one_launch_enabled() &&
-                       pdrnn_lstm_sw_step_ok((int)NL, (int)B, (int)T) == 1;
   Tensor head_slab = at::empty({B, PH}, opts);
-  // Above one residency round the BPTT defers its weight gradients: the
-  // recurrence writes the gate gradients (into `act`, in place) and the
-  // matrix-core kernel lstm_small_dw forms dW / db over all B*T rows, one slab
-  // row per K chunk (see pdrnn_lstm_small_bwd_dwout).  One round or less keeps
-  // the one-launch step (register-resident dW, no extra launch).
-  const int dw_mode = pdrnn_lstm_small_dwout_ok((int)H, (int)NL, (int)T);
-  const bool dwout = sw || (nb_bwd == 1 && split_bwd == 1 && ((gridb < B && dw_mode == 1) || dw_mode == 2));
-  // deferred dW: sequences per BPTT workgroup; the matrix-core launch forms
-  // dW over fixed K chunks, one slab row each
-  const int nb_dw = dwout ? pdrnn_lstm_small_bwd_dwout_nb((int)H, (int)NL, (int)T, (int)B) : (int)nb_bwd;
-  // (sequence-in-wave mode 4: the BPTT waves form dW on the matrix cores, one
-  // slab row per sequence, no dW launch)
-  const bool sw_rdw = sw && sw_bmode == 4;
-  const int slab_rows = sw_rdw ? (int)B : dwout ? pdrnn_lstm_small_dw_chunks((int)H, (int)NL, (int)B, (int)T) : gridb;
-  Tensor slab = at::empty({slab_rows, L.P}, opts);
+  Tensor slab = at::empty({p.slab_rows, L.P}, opts);
+  // deferred dW: the fp32 copy of the gathered layer-0 input rows (written by
+  // the sequence-in-wave forward, or by the gate-split deferred-dW backward)
+  const int64_t xg_ld = (I + 3) / 4 * 4;
+  Tensor xg, st_f, st_b;
+  if (dwout) xg = at::empty({(B * T + PADR) * xg_ld + 256}, opts);  // + one DMA job past the last stage
+  if (stamps_enabled()) {
+    st_f = at::zeros({p.stamp_rows_f, p.phase ? 24 : 8}, opts.dtype(at::kLong));
+    st_b = at::zeros({p.grid_dw, 8}, opts.dtype(at::kLong));
+  }
 
+  // ---- fill the argument structs
   PdrnnLstmSmallFwdArgs f{};
   f.prio = prio_env();
-  f.x = reinterpret_cast<const float*>(x.data_ptr());
-  f.x_bf16 = x.scalar_type() == at::kBFloat16;
-  f.idx = gathered ? idx->data_ptr<int64_t>() : nullptr;
-  f.x_sb = x.stride(0); f.x_st = x.stride(1);
-  for (int64_t l = 0; l < NL; ++l) {
-    f.w_ih[l] = w[l * 4 + 0].data_ptr<float>();
-    f.w_hh[l] = w[l * 4 + 1].data_ptr<float>();
-    f.b_ih[l] = w[l * 4 + 2].data_ptr<float>();
-    f.b_hh[l] = w[l * 4 + 3].data_ptr<float>();
-  }
+  set_input(f, x, idx, true);
+  set_weights(f, w, NL);
   f.hseq = hseq_buf.data_ptr<float>() + H; f.act = act.data_ptr<float>();
   f.hn = hn.data_ptr<float>(); f.cn = cn.data_ptr<float>();
   f.head_w = head_w.data_ptr<float>();
@@ -549,91 +617,53 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
   f.slab = head_slab.data_ptr<float>(); f.dh_top = dh_top.data_ptr<float>();
   f.slab_P = PH; f.head_off_w = 0; f.head_off_b = C * H; f.stat_off = P_head;
   f.inv_batch = 1.f / (float)std::max<int64_t>(B, 1);
-  f.C = (int)C;
-  f.B = (int)B; f.T = (int)T; f.I = (int)I; f.NL = (int)NL; f.cell = (int)cell;
-  f.w_bf16 = round_bf16 ? 1 : 0;
-  hipStream_t st = cur_stream();
-  // deferred dW: the fp32 copy of the gathered layer-0 input rows (written by
-  // the sequence-in-wave forward, or by the gate-split deferred-dW backward)
-  const int64_t xg_ld = (I + 3) / 4 * 4;
-  Tensor xg;
-  if (dwout) xg = at::empty({(B * T + PADR) * xg_ld + 256}, opts);  // + one DMA job past the last stage
+  f.C = (int)C; f.NL = (int)NL; f.cell = (int)cell; f.w_bf16 = round_bf16 ? 1 : 0;
   if (sw) { f.xg_out = xg.data_ptr<float>(); f.xg_ld = (int)xg_ld; }
-  // sequences per sequence-in-wave workgroup: two in modes 1 / 3 (mode 5,
-  // the four-wave forward, runs one)
-  const int sw_fnb = sw ? pdrnn_lstm_sw_nb(sw_fmode) : 1, sw_bnb = sw ? pdrnn_lstm_sw_nb(sw_bmode) : 1;
-  Tensor st_f, st_b;
-  // PDRNN_TUNE sw_phase=1 (with PDRNN_LSTM_STAMPS): the phase-stamped build
-  // of the four-wave forward, rows of 24 (report_phase_stamps)
-  const bool phase = stamps_enabled() && sw && sw_fmode == 5 && cell == 0 && pdrnn_tune_int("sw_phase", 0) != 0;
-  if (stamps_enabled()) {
-    st_f = at::zeros({sw ? (B + sw_fnb - 1) / sw_fnb : (B + nb_fwd - 1) / nb_fwd, phase ? 24 : 8},
-                     opts.dtype(at::kLong));
-    f.phase_stamps = phase ? 1 : 0;
-    st_b = at::zeros({sw ? (B + sw_bnb - 1) / sw_bnb : gridb, 8}, opts.dtype(at::kLong));
-    f.stamps = reinterpret_cast<uint64_t*>(st_f.data_ptr<int64_t>());
-  }
-  // latency regime (one sequence per workgroup in both passes): forward,
-  // head/CE and BPTT in one launch; otherwise the forward launches here
-  const bool one_launch = !dwout && !st_f.defined() &&
-      pdrnn_lstm_small_step_ok((int)H, (int)NL, (int)B, (int)nb_fwd, (int)split_fwd, (int)nb_bwd, (int)split_bwd,
-                               gridb) == 1;
-  if (sw_step) {
-    // (launched with the backward below)
-  } else if (sw) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_fwd(&f, sw_fmode, st));
-  else if (!one_launch) HIP_LAUNCH_CHECK(pdrnn_lstm_small_fwd(&f, (int)H, (int)nb_fwd, (int)split_fwd, 1, st));
+  if (st_f.defined()) { f.phase_stamps = p.phase ? 1 : 0; f.stamps = reinterpret_cast<uint64_t*>(st_f.data_ptr<int64_t>()); }
 
   PdrnnLstmSmallBwdArgs bk{};
   bk.prio = prio_env();
-  bk.x = f.x; bk.x_bf16 = f.x_bf16; bk.idx = f.idx; bk.x_sb = f.x_sb; bk.x_st = f.x_st;
-  for (int64_t l = 0; l < NL; ++l) {
-    bk.w_ih[l] = f.w_ih[l]; bk.w_hh[l] = f.w_hh[l];
-    bk.off_wih[l] = L.off_wih[l]; bk.off_whh[l] = L.off_whh[l];
-    bk.off_bih[l] = L.off_bih[l]; bk.off_bhh[l] = L.off_bhh[l];
-  }
+  set_input(bk, x, idx, true);
+  set_weights(bk, w, NL);
+  set_offsets(bk, L, NL);
   bk.hseq = f.hseq; bk.act = f.act;
   bk.dhn = dh_top.data_ptr<float>(); bk.dhn_top_only = 1;
-  bk.slab = slab.data_ptr<float>(); bk.P = L.P;
-  bk.B = (int)B; bk.T = (int)T; bk.I = (int)I; bk.NL = (int)NL; bk.cell = (int)cell;
-  bk.w_bf16 = f.w_bf16;
-  int grid_dw = gridb;
+  bk.slab = slab.data_ptr<float>();
+  bk.NL = (int)NL; bk.cell = (int)cell; bk.w_bf16 = f.w_bf16;
   if (dwout) {
-    grid_dw = sw ? (int)((B + sw_bnb - 1) / sw_bnb)
-                 : pdrnn_lstm_small_bwd_dwout_grid((int)H, (int)NL, (int)T, (int)B, nb_dw);
-    TORCH_CHECK(grid_dw > 0, "deferred-dW backward: no resident grid");
-    if (st_f.defined() && !sw) {
-      st_b = at::zeros({grid_dw, 8}, opts.dtype(at::kLong));
-      bk.stamps = reinterpret_cast<uint64_t*>(st_b.data_ptr<int64_t>());
-    }
-    bk.dg_out = f.act;  // in place: each row lane overwrites the activation it has consumed
-    bk.dg_st = 5 * H;
-    bk.xg_out = xg.data_ptr<float>();
-    bk.xg_ld = (int)xg_ld;
+    bk.dg_out = f.act; bk.dg_st = 5 * H;  // in place: each row lane overwrites the activation it has consumed
+    bk.xg_out = xg.data_ptr<float>(); bk.xg_ld = (int)xg_ld;
   }
   if (st_b.defined()) bk.stamps = reinterpret_cast<uint64_t*>(st_b.data_ptr<int64_t>());
+
   PdrnnLstmSmallDwArgs dw{};
   if (dwout) {
     dw.xg = xg.data_ptr<float>(); dw.xg_ld = bk.xg_ld;
     dw.hseq = f.hseq; dw.dg = f.act; dw.dg_st = 5 * H;
-    dw.slab = slab.data_ptr<float>(); dw.P = L.P;
-    for (int64_t l = 0; l < NL; ++l) {
-      dw.off_wih[l] = L.off_wih[l]; dw.off_whh[l] = L.off_whh[l];
-      dw.off_bih[l] = L.off_bih[l]; dw.off_bhh[l] = L.off_bhh[l];
-    }
-    dw.B = (int)B; dw.T = (int)T; dw.I = (int)I; dw.NL = (int)NL; dw.chunks = slab_rows;
+    dw.slab = slab.data_ptr<float>();
+    set_offsets(dw, L, NL);
+    dw.B = (int)B; dw.T = (int)T; dw.I = (int)I; dw.NL = (int)NL; dw.chunks = p.slab_rows;
   }
-  if (sw_step) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_step(&f, &bk, st));
-  else if (sw) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_bwd(&bk, sw_bmode, st));
-  else if (one_launch) HIP_LAUNCH_CHECK(pdrnn_lstm_small_step(&f, &bk, (int)H, st));
-  else if (dwout) HIP_LAUNCH_CHECK(pdrnn_lstm_small_bwd_dwout(&bk, (int)H, grid_dw, nb_dw, st));
-  else HIP_LAUNCH_CHECK(pdrnn_lstm_small_bwd(&bk, (int)H, (int)nb_bwd, (int)split_bwd, gridb, st));
-  if (dwout && !sw_rdw) HIP_LAUNCH_CHECK(pdrnn_lstm_small_dw(&dw, (int)H, st));
+
+  // ---- launch
+  hipStream_t st = cur_stream();
+  if (p.sw_step) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_step(&f, &bk, st));
+  else if (p.one_launch) HIP_LAUNCH_CHECK(pdrnn_lstm_small_step(&f, &bk, (int)H, st));
+  else {
+    HIP_LAUNCH_CHECK(sw ? pdrnn_lstm_sw_fwd(&f, p.sw_fmode, st)
+                        : pdrnn_lstm_small_fwd(&f, (int)H, p.nb_fwd, p.split_fwd, 1, st));
+    HIP_LAUNCH_CHECK(sw      ? pdrnn_lstm_sw_bwd(&bk, p.sw_bmode, st)
+                     : dwout ? pdrnn_lstm_small_bwd_dwout(&bk, (int)H, p.grid_dw, p.nb_dw, st)
+                             : pdrnn_lstm_small_bwd(&bk, (int)H, p.nb_bwd, p.split_bwd, p.gridb, st));
+  }
+  if (dwout && !p.sw_rdw) HIP_LAUNCH_CHECK(pdrnn_lstm_small_dw(&dw, (int)H, st));
   if (st_f.defined()) {
     const int bw_iters = sw ? (int)(T + NL - 1)
-                            : (int)(T + 2 * (NL - 1)) * (int)((B + (int64_t)grid_dw * nb_dw - 1) / ((int64_t)grid_dw * nb_dw));
-    if (phase) report_phase_stamps(st_f);
+                            : (int)(T + 2 * (NL - 1)) *
+                                  (int)((B + (int64_t)p.grid_dw * p.nb_dw - 1) / ((int64_t)p.grid_dw * p.nb_dw));
+    if (p.phase) report_phase_stamps(st_f);
     report_stamps(sw ? "fwd(head step, seq-in-wave)" : "fwd(head step)",
-                  phase ? st_f.narrow(1, 0, 8).contiguous() : st_f, (int)(T + NL - 1));
+                  p.phase ? st_f.narrow(1, 0, 8).contiguous() : st_f, (int)(T + NL - 1));
     report_stamps(sw ? "bwd(head step, seq-in-wave, deferred dW)"
                      : dwout ? "bwd(head step, lean, deferred dW)" : "bwd(head step, lean)",
                   st_b, bw_iters);
@@ -666,7 +696,7 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
       ad.ticket = reinterpret_cast<unsigned int*>(adam_ticket->data_ptr<int>());
     }
   }
-  HIP_LAUNCH_CHECK(pdrnn_slab_reduce_adam(fold_adam ? &ad : nullptr, slab.data_ptr<float>(), slab_rows, P_rnn, L.P,
+  HIP_LAUNCH_CHECK(pdrnn_slab_reduce_adam(fold_adam ? &ad : nullptr, slab.data_ptr<float>(), p.slab_rows, P_rnn, L.P,
                                           colmap, head_slab.data_ptr<float>(), B, PH, P_params,
                                           flat_grad.data_ptr<float>(), stats.data_ptr<float>(), slot_step,
                                           (int)stats_slot_offset, ring_rows, st));
@@ -1641,21 +1671,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("lstm_small_step_one_launch", [](int64_t H, int64_t NL, int64_t T, int64_t B, int64_t nb_fwd,
                                          int64_t split_fwd, int64_t nb_bwd, int64_t split_bwd) {
-    if (split_fwd <= 0) split_fwd = pdrnn_lstm_small_max_split((int)H, (int)NL, 0);
-    if (split_bwd <= 0) split_bwd = pdrnn_lstm_small_max_split((int)H, (int)NL, 1);
-    if (nb_fwd <= 0) nb_fwd = 1;
-    if (nb_bwd <= 0) nb_bwd = 1;
-    const int gridb = pdrnn_lstm_small_bwd_grid((int)H, (int)NL, (int)T, (int)B, (int)nb_bwd, (int)split_bwd);
-    return pdrnn_lstm_small_step_ok((int)H, (int)NL, (int)B, (int)nb_fwd, (int)split_fwd, (int)nb_bwd,
-                                    (int)split_bwd, gridb) != 0;
-  }, "the fused training step runs forward + head/CE + BPTT as one launch for this shape");
+    const HeadStepPlan p = plan_small_family(H, NL, T, B, nb_fwd, split_fwd, nb_bwd, split_bwd);
+    return !p.error && p.one_launch;
+  }, "the fused training step (gate-split / K-split family) runs forward + head/CE + BPTT as one launch for this shape");
   m.def("lstm_small_step_deferred_dw", [](int64_t H, int64_t NL, int64_t T, int64_t B) {
     // the fused step's default single-sequence backward (nb = 1, unit-group map)
-    const int split_bwd = pdrnn_lstm_small_max_split((int)H, (int)NL, 1);
-    const int gridb = pdrnn_lstm_small_bwd_grid((int)H, (int)NL, (int)T, (int)B, 1, split_bwd);
-    const int mode = pdrnn_lstm_small_dwout_ok((int)H, (int)NL, (int)T);
-    return split_bwd == 1 && ((gridb < B && mode == 1) || mode == 2);
-  }, "the fused training step defers the weight gradients to the matrix-core dW kernel for this shape");
+    const HeadStepPlan p = plan_small_family(H, NL, T, B, 0, 0, 0, 0);
+    return !p.error && p.dwout;
+  }, "the fused training step (gate-split / K-split family) defers the weight gradients to the matrix-core dW "
+     "kernel for this shape");
+  m.def("lstm_head_step_plan", [](int64_t H, int64_t I, int64_t NL, int64_t T, int64_t B, int64_t cell, int64_t nb_fwd,
+                                  int64_t split_fwd, int64_t nb_bwd, int64_t split_bwd, const optional<int64_t>& sw,
+                                  const optional<bool>& stamps) {
+    HeadStepShape s{(int)H, (int)I, (int)NL, (int)T, (int)B, (int)cell, (int)nb_fwd, (int)split_fwd, (int)nb_bwd,
+                    (int)split_bwd};
+    if (sw.has_value()) { s.sw_on = *sw != 0; s.sw_one_launch = *sw != 0 && *sw != 2; }
+    if (stamps.has_value()) s.stamps = *stamps;
+    const HeadStepPlan p = plan_head_step(s);
+    TORCH_CHECK(!p.error, p.error);
+    py::dict d;
+    d["path"] = p.path;
+    d["nb_fwd"] = p.nb_fwd; d["split_fwd"] = p.split_fwd; d["nb_bwd"] = p.nb_bwd; d["split_bwd"] = p.split_bwd;
+    d["sw"] = p.sw; d["sw_fmode"] = p.sw_fmode; d["sw_bmode"] = p.sw_bmode; d["sw_step"] = p.sw_step;
+    d["one_launch"] = p.one_launch; d["dwout"] = p.dwout;
+    d["gridb"] = p.gridb; d["nb_dw"] = p.nb_dw; d["grid_dw"] = p.grid_dw; d["slab_rows"] = p.slab_rows;
+    d["stamps_fwd"] = py::make_tuple(p.stamp_rows_f, p.phase ? 24 : 8);
+    d["stamps_bwd"] = py::make_tuple(p.grid_dw, 8);
+    return d;
+  }, "what lstm_head_train_step does for this shape: `path` (sw_one_launch, sw_two_launch, one_launch, deferred_dw "
+     "or register_dw), the launch geometry and the stamp shapes.  sw (0 / 1 / 2, as PDRNN_SW) and stamps default "
+     "to the environment's switches",
+        py::arg("H"), py::arg("I"), py::arg("NL"), py::arg("T"), py::arg("B"), py::arg("cell") = 0,
+        py::arg("nb_fwd") = 0, py::arg("split_fwd") = 0, py::arg("nb_bwd") = 0, py::arg("split_bwd") = 0,
+        py::arg("sw") = py::none(), py::arg("stamps") = py::none());
   m.def("lstm_small_dwout_geometry", [](int64_t H, int64_t NL, int64_t T, int64_t B) {
     const int nb = pdrnn_lstm_small_bwd_dwout_nb((int)H, (int)NL, (int)T, (int)B);
     return py::make_tuple(nb, pdrnn_lstm_small_bwd_dwout_grid((int)H, (int)NL, (int)T, (int)B, nb));

@@ -146,11 +146,11 @@ hipError_t pdrnn_lstm_small_bwd_dwout(const PdrnnLstmSmallBwdArgs* a, int H, int
 int pdrnn_lstm_small_bwd_dwout_nb(int H, int NL, int T, int B);
 int pdrnn_lstm_small_bwd_dwout_grid(int H, int NL, int T, int B, int nb);
 
-// Query the launch geometry chosen for (H, B): returns grid size (number of slab rows).
-int pdrnn_lstm_small_grid(int H, int B, int nb);
+// H in {16, 32} with 1..4 layers, H = 64 with one layer; 1 <= I <= H
 int pdrnn_lstm_small_supported(int H, int I, int NL);
 int pdrnn_lstm_small_max_split(int H, int NL, int backward);
-// split = lanes per hidden unit (forward S in {2,4,8}; backward S2 in {2,4})
+// split: 1 = gate-split forward / unit-group backward, 2 = 2-lane K-split
+// forward / row-split backward (pdrnn_lstm_small_max_split: the widest that fits)
 hipError_t pdrnn_lstm_small_fwd(const PdrnnLstmSmallFwdArgs* a, int H, int nb, int split, int save,
                                 hipStream_t stream);
 // grid <= 0: natural grid (persistent for the unit-group map); query with _bwd_grid
@@ -184,24 +184,10 @@ hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream
 hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t stream);
 
 // Column sums of a [rows, P] fp32 slab into out[P] (out = beta*out + sum).
-// Two deterministic passes through `work` ([split, P] floats, split <= 64).
+// Two deterministic passes through `work` ([split, P] floats, split <= 64)
+// (kernels/adam.hip, beside the fused step's one-pass pdrnn_slab_reduce_adam).
 hipError_t pdrnn_slab_reduce(const float* slab, int64_t rows, int64_t P, float* out, float beta,
                              float* work, int split, hipStream_t stream);
-// Two slabs reduced side by side (columns of A then of B); the first n_out
-// summed columns go to out, the rest to out_tail.
-hipError_t pdrnn_slab2_reduce(const float* A, int64_t rowsA, int64_t PA, const float* Bs, int64_t rowsB, int64_t PB,
-                              int64_t n_out, float* out, float* out_tail, float* work, int split, const int* colmap,
-                              int64_t ldA, hipStream_t stream);
-// First pass only (work[split][PA+PB] partial column sums); the second pass
-// can be fused into its consumer (pdrnn_adam_partials).
-// colmap (optional, with ldA = A's leading dimension): output column p < PA
-// reads A column colmap[p] (GRU packed layout -> nn.GRU order); NULL = identity
-hipError_t pdrnn_slab2_reduce_pass1(const float* A, int64_t rowsA, int64_t PA, const float* Bs, int64_t rowsB,
-                                   int64_t PB, float* work, int split, const int* colmap, int64_t ldA,
-                                   hipStream_t stream);
-// Same, with columns [P_a, P) written to out_b instead (e.g. loss statistics).
-hipError_t pdrnn_slab_reduce2(const float* slab, int64_t rows, int64_t P, int64_t P_a, float* out_a,
-                              float* out_b, float* work, int split, hipStream_t stream);
 
 // ----------------------------------------------------------------------------
 // Fused cross-entropy (+ accuracy): mean loss over valid rows, dlogits saved.

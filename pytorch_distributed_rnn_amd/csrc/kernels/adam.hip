@@ -137,6 +137,34 @@ __global__ void __launch_bounds__(256) adam_partials_kernel(PdrnnAdamArgs a, con
   }
 }
 
+// Column-sum of a [rows, P] slab: pass 1 sums row chunks into work[split, P].
+__global__ void slab_reduce_pass1(const float* __restrict__ slab, int64_t rows, int64_t P,
+                                  float* __restrict__ work, int split) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int sp = blockIdx.y;
+  if (p >= P) return;
+  const int64_t r0 = rows * sp / split, r1 = rows * (sp + 1) / split;
+  float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+  int64_t r = r0;
+  for (; r + 4 <= r1; r += 4) {
+    acc0 += slab[(r + 0) * P + p];
+    acc1 += slab[(r + 1) * P + p];
+    acc2 += slab[(r + 2) * P + p];
+    acc3 += slab[(r + 3) * P + p];
+  }
+  for (; r < r1; ++r) acc0 += slab[r * P + p];
+  work[(int64_t)sp * P + p] = (acc0 + acc1) + (acc2 + acc3);
+}
+
+__global__ void slab_reduce_pass2(const float* __restrict__ work, int64_t P, int split,
+                                  float* __restrict__ out, float beta) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  float acc = 0.f;
+  for (int sp = 0; sp < split; ++sp) acc += work[(int64_t)sp * P + p];
+  out[p] = beta == 0.f ? acc : fmaf(beta, out[p], acc);
+}
+
 // One-pass column reduction of the fused step's two gradient slabs into the
 // flat gradient, with the Adam update folded in (a.param != nullptr; the
 // single-process step) -- replaces the two-pass reduction (slab2_reduce_pass1
@@ -282,6 +310,20 @@ __global__ void __launch_bounds__(256) scale_flat_kernel(float* __restrict__ g, 
 
 }  // namespace
 }  // namespace pdrnn
+
+extern "C" hipError_t pdrnn_slab_reduce(const float* slab, int64_t rows, int64_t P, float* out, float beta,
+                                        float* work, int split, hipStream_t stream) {
+  if (split < 1) split = 1;
+  if (split > 64) split = 64;
+  if (split > rows) split = (int)rows > 0 ? (int)rows : 1;
+  const int threads = 256;
+  dim3 g1((unsigned)((P + threads - 1) / threads), (unsigned)split);
+  hipLaunchKernelGGL(pdrnn::slab_reduce_pass1, g1, dim3(threads), 0, stream, slab, rows, P, work, split);
+  PDRNN_HIP_CHECK(hipGetLastError());
+  dim3 g2((unsigned)((P + threads - 1) / threads));
+  hipLaunchKernelGGL(pdrnn::slab_reduce_pass2, g2, dim3(threads), 0, stream, work, P, split, out, beta);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t pdrnn_slab_reduce_adam(const PdrnnAdamArgs* a, const float* A, int64_t rowsA, int64_t PA,
                                             int64_t ldA, const int* colmap, const float* Bs, int64_t rowsB,

@@ -10,26 +10,37 @@
 //    so the stack costs T + NL - 1 dependent steps instead of NL * T.  One
 //    workgroup barrier per iteration; layer hand-offs go through double-
 //    buffered LDS vectors.
-//  * Forward lane map: a layer group is H*S lanes, lane = (unit u, K-slice s).
-//    Each lane keeps ITS rows of [W_ih | W_hh] (4 gates x 2H/S columns) in
-//    VGPRs for the whole launch and reads its K-slice of [x_t | h_{t-1}] from
-//    LDS with broadcast ds_read_b128.  The S partial dot products of a unit
-//    are combined with DPP quad permutes (no LDS), after which every lane of
-//    the unit holds all four gates and updates c/h redundantly.
-//  * Backward lane map (per layer group of 2H*S2 lanes): a "row" role (lane =
-//    gate row r = q*H+u, computes dgates) and a "column" role (lane = column k
-//    of [W_ih | W_hh] x row-slice s2) that owns W[r-slice][k] AND accumulates
-//    dW[r-slice][k] in registers across all timesteps and all NB sequences
-//    (the weight gradient never round-trips through HBM per timestep).  The
-//    column role produces dh_{t-1} (recurrent) and d(input) for the layer
-//    below with the same FMAs.  Partial per-workgroup dW are written to a slab
-//    that a deterministic two-pass reduction sums (pdrnn_slab_reduce).
+//  * Forward, gate-split map (the default, lstm_small_fwd_gs_kernel): a layer
+//    group is 4H lanes, lane = (unit u, gate q).  Each lane keeps ITS row of
+//    [W_ih | W_hh] in VGPRs for the whole launch and reads the whole
+//    [x_t | h_{t-1}] operand vector from LDS with broadcast ds_read_b128; the
+//    four gates of a unit meet through DPP quad permutes (no LDS).  Above one
+//    residency round (B > 1024 at H = 32) the host picks the 2-lane K-split
+//    map instead (lstm_small_fwd_kernel: lane = (unit, K-slice), each lane
+//    reads half the operand vector and holds all four gates of its slice).
+//  * Backward, unit-group map (the default, lstm_small_bwd_gs_kernel): a layer
+//    group is H*L lanes, L = 4 lanes per hidden unit (8 at H = 64).  In the
+//    row phase a lane computes the gate gradients of its unit; in the column
+//    phase it owns a 4H/L row slice of column k of [W_ih | W_hh] AND
+//    accumulates dW of that slice in registers across all timesteps and all
+//    NB sequences (the weight gradient never round-trips through HBM per
+//    timestep), producing dh_{t-1} and d(input) for the layer below with the
+//    same FMAs.  The grid is persistent (resident workgroups walk the batch
+//    tiles); partial per-workgroup dW go to a slab that a deterministic
+//    reduction sums (pdrnn_slab_reduce / pdrnn_slab_reduce_adam, adam.hip).
+//    Variants on the same body: the deferred-dW backward (writes the gate
+//    gradients for the matrix-core kernel lstm_small_dw.hip) and the
+//    one-launch step (forward + head/CE + BPTT of one sequence per workgroup).
+//    The older row/column split (lstm_small_bwd_kernel) is kept behind
+//    PDRNN_TUNE split_bwd=2.
 //  * Layer-0 input is zero-padded to H columns so every layer has K = 2H:
 //    layers are load-balanced in the pipeline and there is one code path.
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"
 
 #include <cstring>
+#include <type_traits>
+#include <vector>
 
 namespace pdrnn {
 namespace {
@@ -1387,422 +1398,176 @@ __global__ void __launch_bounds__(512) lstm_small_step_gs_kernel(PdrnnLstmSmallF
   lstm_small_bwd_gs_body<H, 4, 1, XLDS, true, CELL>(b, xs_off, &wcols, dh_lds);
 }
 
-// Column-sum of a [rows, P] slab: pass 1 sums row chunks into work[split, P].
-__global__ void slab_reduce_pass1(const float* __restrict__ slab, int64_t rows, int64_t P,
-                                  float* __restrict__ work, int split) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int sp = blockIdx.y;
-  if (p >= P) return;
-  const int64_t r0 = rows * sp / split, r1 = rows * (sp + 1) / split;
-  float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-  int64_t r = r0;
-  for (; r + 4 <= r1; r += 4) {
-    acc0 += slab[(r + 0) * P + p];
-    acc1 += slab[(r + 1) * P + p];
-    acc2 += slab[(r + 2) * P + p];
-    acc3 += slab[(r + 3) * P + p];
-  }
-  for (; r < r1; ++r) acc0 += slab[r * P + p];
-  work[(int64_t)sp * P + p] = (acc0 + acc1) + (acc2 + acc3);
+// ---- Host side -------------------------------------------------------------
+// Every kernel family has ONE function (<family>_kernel) that maps the runtime
+// flags of a launch to its instantiation -- entry point, sequences per
+// workgroup, block size, dynamic LDS -- and launch() / resident() work on that,
+// so a launcher and its grid query cannot disagree.  with_int / with_bools turn
+// runtime values into integral_constants; `if constexpr` in the family
+// functions keeps the instantiated set to what is dispatched.
+struct Kernel { const void* fn; int nb, block; size_t lds; hipError_t err; };  // nb: sequences per workgroup
+inline Kernel no_kernel(hipError_t e) { return {nullptr, 1, 0, 0, e}; }
+template <class K>
+Kernel kernel(K* fn, int nb, int block, size_t lds) { return {(const void*)fn, nb, block, lds, hipSuccess}; }
+
+// f(integral_constant<int, N>) for the N of Ns that equals v, else `miss`
+template <int... Ns, class R, class F>
+R with_int(int v, R miss, F&& f) {
+  (void)((v == Ns && (miss = f(std::integral_constant<int, Ns>{}), true)) || ...);
+  return miss;
+}
+// f(bool_constant...) for the given runtime flags, in order
+template <class F> auto with_bools(F&& f) { return f(); }
+template <class F, class... Rest>
+auto with_bools(F&& f, bool flag, Rest... rest) {
+  auto on = [&](auto... c) { return f(std::true_type{}, c...); };
+  auto off = [&](auto... c) { return f(std::false_type{}, c...); };
+  return flag ? with_bools(on, rest...) : with_bools(off, rest...);
 }
 
-__global__ void slab_reduce_pass2(const float* __restrict__ work, int64_t P, int split,
-                                  float* __restrict__ out, float beta) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  float acc = 0.f;
-  for (int sp = 0; sp < split; ++sp) acc += work[(int64_t)sp * P + p];
-  out[p] = beta == 0.f ? acc : fmaf(beta, out[p], acc);
-}
+// ... and f(integral_constant<int, H>) for the hidden sizes the kernels are built for
+template <class R, class F> R with_hidden(int H, R miss, F&& f) { return with_int<16, 32, 64>(H, miss, f); }
 
-// pass 1 over two slabs side by side: columns [0, PA) from A, [PA, PA+PB) from B.
-// colmap (optional): output column p < PA reads A column colmap[p] of an A
-// slab with leading dimension ldA (the GRU's packed 4-block layout -> nn.GRU
-// parameter order, zero blocks dropped).
-__global__ void slab2_reduce_pass1(const float* __restrict__ A, int64_t rowsA, int64_t PA,
-                                   const float* __restrict__ Bs, int64_t rowsB, int64_t PB,
-                                   float* __restrict__ work, int split, const int* __restrict__ colmap,
-                                   int64_t ldA) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int sp = blockIdx.y;
-  const int64_t P = PA + PB;
-  if (p >= P) return;
-  const bool inA = p < PA;
-  const float* src = inA ? A + (colmap ? colmap[p] : p) : Bs + (p - PA);
-  const int64_t ld = inA ? ldA : PB;
-  const int64_t rows = inA ? rowsA : rowsB;
-  const int64_t r0 = rows * sp / split, r1 = rows * (sp + 1) / split;
-  // 8 independent loads in flight per thread (the head slab has B rows over
-  // ~200 columns: few threads, long columns -- latency-bound otherwise)
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int64_t r = r0;
-  for (; r + 8 <= r1; r += 8) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] += src[(r + k) * ld];
-  }
-  for (int k = 0; r < r1; ++r, ++k) acc[k] += src[r * ld];
-  work[(int64_t)sp * P + p] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-}
-
-__global__ void slab_reduce_pass2_split(const float* __restrict__ work, int64_t P, int64_t Pa, int split,
-                                        float* __restrict__ out_a, float* __restrict__ out_b) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  float acc = 0.f;
-  for (int sp = 0; sp < split; ++sp) acc += work[(int64_t)sp * P + p];
-  if (p < Pa) out_a[p] = acc;
-  else out_b[p - Pa] = acc;
-}
-
-template <int H, int S, int NB, bool SAVE>
-hipError_t launch_fwd(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  constexpr int LANES = H * S;
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = a->NL * LANES;
-  const size_t lds = sizeof(float) * NB * a->NL * 2 * (2 * H);
-  const size_t xbytes = sizeof(float) * (size_t)NB * a->T * H;
-  if constexpr (SAVE) {
-    if (a->head_w) {  // fused training step: classifier head + CE epilogue
-      if (a->C > 16) return hipErrorInvalidValue;
-      if (xbytes <= (size_t)kXldsBytes)
-        hipLaunchKernelGGL((lstm_small_fwd_kernel<H, S, NB, true, true, true>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-      else
-        hipLaunchKernelGGL((lstm_small_fwd_kernel<H, S, NB, true, false, true>), dim3(grid), dim3(block), lds, st, *a);
-      return hipGetLastError();
-    }
-  }
-  if (xbytes <= (size_t)kXldsBytes)
-    hipLaunchKernelGGL((lstm_small_fwd_kernel<H, S, NB, SAVE, true>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else
-    hipLaunchKernelGGL((lstm_small_fwd_kernel<H, S, NB, SAVE, false>), dim3(grid), dim3(block), lds, st, *a);
+template <class... Args>
+hipError_t launch(const Kernel& k, int grid, hipStream_t st, const Args*... args) {
+  if (k.err != hipSuccess) return k.err;
+  void* argv[] = {const_cast<Args*>(args)...};
+  (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), argv, k.lds, st);
   return hipGetLastError();
 }
 
-template <int H, int NB, bool SAVE>
-hipError_t launch_fwd_gs(const PdrnnLstmSmallFwdArgs* a, hipStream_t st);
-
-// GRU forward: NB sequences per workgroup (2 above one residency round: one
-// sequence per 4-wave workgroup holds ~150 VGPRs, 3 workgroups per CU); the
-// classifier head + CE epilogue of the fused training step (SAVE + head_w) is
-// shared with the LSTM.
-template <int H, int NB, bool SAVE>
-hipError_t launch_fwd_gs_gru(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = a->NL * 4 * H;
-  const size_t lds = sizeof(float) * NB * a->NL * 2 * (2 * H);
-  const size_t xbytes = sizeof(float) * (size_t)NB * a->T * H;
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (a->head_w) {
-    if constexpr (SAVE) {
-      if (a->C > 16) return hipErrorInvalidValue;
-      if (xl) hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, true, true, true, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-      else hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, true, false, true, 1>), dim3(grid), dim3(block), lds, st, *a);
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
-  if (xl)
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, SAVE, true, false, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, SAVE, false, false, 1>), dim3(grid), dim3(block), lds, st, *a);
-  return hipGetLastError();
-}
-
-template <int H, int NB, bool SAVE>
-hipError_t launch_fwd_gs(const PdrnnLstmSmallFwdArgs* a, hipStream_t st);
-
-// GRU forward: one sequence per workgroup; the classifier head + CE epilogue
-// of the fused training step (SAVE + head_w) is shared with the LSTM.
-template <int H, bool SAVE>
-hipError_t launch_fwd_gs_gru(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  const int grid = a->B;
-  const int block = a->NL * 4 * H;
-  const size_t lds = sizeof(float) * a->NL * 2 * (2 * H);
-  const size_t xbytes = sizeof(float) * (size_t)a->T * H;
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (a->head_w) {
-    if constexpr (SAVE) {
-      if (a->C > 16) return hipErrorInvalidValue;
-      if (xl) hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, 1, true, true, true, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-      else hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, 1, true, false, true, 1>), dim3(grid), dim3(block), lds, st, *a);
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
-  if (xl)
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, 1, SAVE, true, false, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, 1, SAVE, false, false, 1>), dim3(grid), dim3(block), lds, st, *a);
-  return hipGetLastError();
-}
-
-template <int H, int NB, bool SAVE>
-hipError_t launch_fwd_gs(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = a->NL * 4 * H;
-  const size_t lds = sizeof(float) * NB * a->NL * 2 * (2 * H);
-  const size_t xbytes = sizeof(float) * (size_t)NB * a->T * H;
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if constexpr (SAVE) {
-    if (a->head_w) {
-      if (a->C > 16) return hipErrorInvalidValue;
-      if (xl) hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, true, true, true>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-      else hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, true, false, true>), dim3(grid), dim3(block), lds, st, *a);
-      return hipGetLastError();
-    }
-  }
-  if (xl)
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, SAVE, true, false>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else
-    hipLaunchKernelGGL((lstm_small_fwd_gs_kernel<H, NB, SAVE, false, false>), dim3(grid), dim3(block), lds, st, *a);
-  return hipGetLastError();
-}
-
-// lanes per hidden unit of the unit-group backward: 8 at H = 64 (row slices
-// of 32), else 4
-template <int H>
-int bwd_gs_lanes(int NL) {
-  (void)NL;
-  return H == 64 ? 8 : 4;
-}
-
-// Persistent grid for the backward: as many workgroups as can be resident
-// (occupancy query x CU count), capped by the number of batch tiles.
-template <int H, int L, int NB, bool XLDS, bool LEAN>
-int bwd_gs_resident(int NL, size_t lds) {
-  // one-entry cache per instantiation (the query costs a driver round trip)
-  static thread_local int c_dev = -1, c_nl = -1, c_val = 0;
-  static thread_local size_t c_lds = 0;
+// Workgroups of a kernel that can be resident on the current device (occupancy
+// query x CU count).  The query costs a driver round trip: cached per thread.
+int resident(const Kernel& k) {
+  struct Entry { const void* fn; int dev, block; size_t lds; int val; };
+  static thread_local std::vector<Entry> cache;
   int per_cu = 0, cus = 0, dev = 0;
-  hipGetDevice(&dev);
-  if (dev == c_dev && NL == c_nl && lds == c_lds) return c_val;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_small_bwd_gs_kernel<H, L, NB, XLDS, LEAN>, NL * H * L, lds);
-  if (per_cu < 1) per_cu = 1;
-  if (cus < 1) cus = 1;
-  c_dev = dev; c_nl = NL; c_lds = lds; c_val = per_cu * cus;
-  return c_val;
+  (void)hipGetDevice(&dev);
+  for (const Entry& e : cache)
+    if (e.fn == k.fn && e.dev == dev && e.block == k.block && e.lds == k.lds) return e.val;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, k.block, k.lds);
+  const int val = (per_cu < 1 ? 1 : per_cu) * (cus < 1 ? 1 : cus);
+  if (cache.size() >= 64) cache.clear();  // (sequence lengths come and go)
+  cache.push_back({k.fn, dev, k.block, k.lds, val});
+  return val;
 }
 
-template <int H, int NB>
-size_t bwd_gs_lds(int NL) {
-  // dg slices padded by 4 floats per lane slice (L <= 8 lanes per unit)
-  return sizeof(float) * NB * NL * 2 * (4 * H + 8 * 4 + H);
+inline int tiles(int B, int nb) { return (B + nb - 1) / nb; }
+// Persistent grid of the backward: resident workgroups, capped by the batch tiles.
+int persistent_grid(const Kernel& k, int B) {
+  if (k.err != hipSuccess) return -1;
+  const int t = tiles(B, k.nb), cap = resident(k);
+  return t < cap ? t : cap;
 }
-template <int H, int NB>
-size_t bwd_gs_xbytes(int T) { return sizeof(float) * (size_t)NB * T * H; }
 
+// Dynamic LDS: the operand buffers of nb sequences, plus their x image when it fits.
+inline size_t x_bytes(int H, int nb, int T) { return sizeof(float) * (size_t)nb * T * H; }
+inline bool x_in_lds(int H, int nb, int T) { return x_bytes(H, nb, T) <= (size_t)kXldsBytes; }
+inline size_t with_x(size_t lds, int H, int nb, int T) { return lds + (x_in_lds(H, nb, T) ? x_bytes(H, nb, T) : 0); }
+inline size_t fwd_lds(int H, int nb, int NL) { return sizeof(float) * nb * NL * 2 * (2 * H); }
+// (dg slices padded by 4 floats per lane slice, L <= 8 lanes per unit)
+inline size_t bwd_gs_lds(int H, int nb, int NL) { return sizeof(float) * nb * NL * 2 * (4 * H + 8 * 4 + H); }
+
+// lanes per hidden unit of the unit-group backward (row slices of 4H / L = 32 at H = 64)
+template <int H> constexpr int kUnitLanes = H == 64 ? 8 : 4;
+
+// Forward.  split 1: gate-split map (4 lanes per unit, one gate each), LSTM and
+// GRU.  split 2: 2-lane K-split map, LSTM only; its 2H lanes per layer must
+// fill whole waves (H >= 32).  K splits of 4 / 8 lanes per unit are never the
+// widest valid map (a stack that fits them fits the gate-split map) and are not
+// built.  1 or 2 sequences per workgroup; workgroups of at most 512 lanes (the
+// launch bound keeps 256 VGPRs per lane available).  HEAD (with SAVE only): the
+// fused training step's classifier head + CE epilogue.
+template <int H>
+Kernel fwd_kernel(const PdrnnLstmSmallFwdArgs* a, int nb, int split, bool save) {
+  const bool gru = a->cell == 1, head = save && a->head_w;
+  if (gru && split != 1) return no_kernel(hipErrorInvalidConfiguration);
+  if ((split != 1 && split != 2) || (split == 2 && H < 32)) return no_kernel(hipErrorInvalidValue);
+  const int block = a->NL * H * (split == 1 ? 4 : 2);
+  if (block > 512) return no_kernel(hipErrorInvalidConfiguration);
+  if ((gru && a->head_w && !save) || (head && a->C > 16)) return no_kernel(hipErrorInvalidValue);
+  if (split == 1) nb = nb == 2 ? 2 : 1;
+  return with_int<1, 2>(nb, no_kernel(hipErrorInvalidValue), [&](auto nb_c) {
+    constexpr int NB = decltype(nb_c)::value;
+    const size_t lds = with_x(fwd_lds(H, NB, a->NL), H, NB, a->T);
+    return with_bools([&](auto SAVE, auto XLDS, auto HEAD, auto GRU, auto KSPLIT) {
+      if constexpr ((HEAD && !SAVE) || (KSPLIT && (GRU || H < 32))) return no_kernel(hipErrorInvalidValue);
+      else if constexpr (KSPLIT) return kernel(lstm_small_fwd_kernel<H, 2, NB, SAVE, XLDS, HEAD>, NB, block, lds);
+      else return kernel(lstm_small_fwd_gs_kernel<H, NB, SAVE, XLDS, HEAD, GRU ? 1 : 0>, NB, block, lds);
+    }, save, x_in_lds(H, NB, a->T), head, gru, split == 2);
+  });
+}
+
+// the fused training step's backward contract: zero initial state, loss through h_T only
 inline bool bwd_lean(const PdrnnLstmSmallBwdArgs* a) {
   return !a->h0 && !a->c0 && !a->dout && !a->dcn && !a->dx && !a->dh0 && !a->dc0 && a->dhn && a->dhn_top_only;
 }
 
-template <int H, int L, int NB>
-int bwd_gs_grid(const PdrnnLstmSmallBwdArgs* a) {
-  const size_t lds = bwd_gs_lds<H, NB>(a->NL), xbytes = bwd_gs_xbytes<H, NB>(a->T);
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  int cap;
-  if (bwd_lean(a)) cap = xl ? bwd_gs_resident<H, L, NB, true, true>(a->NL, lds + xbytes)
-                            : bwd_gs_resident<H, L, NB, false, true>(a->NL, lds);
-  else cap = xl ? bwd_gs_resident<H, L, NB, true, false>(a->NL, lds + xbytes)
-                : bwd_gs_resident<H, L, NB, false, false>(a->NL, lds);
-  const int tiles = (a->B + NB - 1) / NB;
-  return tiles < cap ? tiles : cap;
+// Unit-group backward with register-resident dW: 1..3 sequences per workgroup
+// for the LSTM at H <= 32, one at H = 64 and for the GRU.
+template <int H>
+Kernel bwd_gs_kernel(int cell, int nb, int NL, int T, bool lean) {
+  constexpr int L = kUnitLanes<H>;
+  if (NL * H * L > 512) return no_kernel(hipErrorInvalidConfiguration);
+  return with_int<1, 2, 3>(nb, no_kernel(hipErrorInvalidConfiguration), [&](auto nb_c) {
+    constexpr int NB = decltype(nb_c)::value;
+    return with_bools([&](auto XLDS, auto LEAN, auto GRU) {
+      if constexpr (NB > 1 && (GRU || H == 64)) return no_kernel(hipErrorInvalidConfiguration);
+      else return kernel(lstm_small_bwd_gs_kernel<H, L, NB, XLDS, LEAN, GRU ? 1 : 0>, NB, NL * H * L,
+                         with_x(bwd_gs_lds(H, NB, NL), H, NB, T));
+    }, x_in_lds(H, NB, T), lean, cell == 1);
+  });
 }
 
-template <int H, int L>
-hipError_t launch_bwd_gs_gru(const PdrnnLstmSmallBwdArgs* a, hipStream_t st, int grid) {
-  const int block = a->NL * H * L;
-  const size_t lds = bwd_gs_lds<H, 1>(a->NL), xbytes = bwd_gs_xbytes<H, 1>(a->T);
-  if (grid <= 0) grid = bwd_gs_grid<H, L, 1>(a);
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (bwd_lean(a)) {  // fused training step: zero initial state, loss through h_T only
-    if (xl) hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, 1, true, true, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-    else hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, 1, false, true, 1>), dim3(grid), dim3(block), lds, st, *a);
-  } else {
-    if (xl) hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, 1, true, false, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-    else hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, 1, false, false, 1>), dim3(grid), dim3(block), lds, st, *a);
-  }
-  return hipGetLastError();
-}
-
-template <int H, int L, int NB>
-hipError_t launch_bwd_gs(const PdrnnLstmSmallBwdArgs* a, hipStream_t st, int grid) {
-  const int block = a->NL * H * L;
-  const size_t lds = bwd_gs_lds<H, NB>(a->NL), xbytes = bwd_gs_xbytes<H, NB>(a->T);
-  if (grid <= 0) grid = bwd_gs_grid<H, L, NB>(a);
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (bwd_lean(a)) {
-    if (xl) hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, NB, true, true>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-    else hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, NB, false, true>), dim3(grid), dim3(block), lds, st, *a);
-  } else {
-    if (xl) hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, NB, true, false>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-    else hipLaunchKernelGGL((lstm_small_bwd_gs_kernel<H, L, NB, false, false>), dim3(grid), dim3(block), lds, st, *a);
-  }
-  return hipGetLastError();
-}
-
-template <int H, int S2, int NB>
-hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, hipStream_t st) {
-  constexpr int G = 2 * H * S2;
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = a->NL * G;
-  const size_t lds = sizeof(float) * NB * a->NL * (4 * H + 2 * H);
-  const size_t xbytes = sizeof(float) * (size_t)NB * a->T * H;
-  if (xbytes <= (size_t)kXldsBytes)
-    hipLaunchKernelGGL((lstm_small_bwd_kernel<H, S2, NB, true>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else
-    hipLaunchKernelGGL((lstm_small_bwd_kernel<H, S2, NB, false>), dim3(grid), dim3(block), lds, st, *a);
-  return hipGetLastError();
-}
-
-// Valid lane splits.  Forward: lanes per layer H*S (multiple of 64),
-// K slice 2H/S float4-aligned and inside one half of [x | h].  Backward:
-// lanes per layer 2H*S2, row slice 4H/S2 a multiple of 16.  Workgroup size
-// NL * lanes <= 512 (launch bound: keeps 256 VGPRs per lane available).
-constexpr bool fwd_ok(int H, int S) {
-  return (H * S) % 64 == 0 && (2 * H / S) % 4 == 0 && H % (2 * H / S) == 0;
-}
-constexpr bool bwd_ok(int H, int S2) { return S2 >= 2 && (4 * H / S2) % 16 == 0 && (2 * H * S2) % 64 == 0; }
-
-template <int H, int S>
-hipError_t dispatch_fwd_s(const PdrnnLstmSmallFwdArgs* a, int nb, int save, hipStream_t st) {
-  if constexpr (!fwd_ok(H, S)) {
-    return hipErrorInvalidValue;
-  } else {
-    if (a->NL * H * S > 512) return hipErrorInvalidConfiguration;
-    if (save) {
-      if (nb == 1) return launch_fwd<H, S, 1, true>(a, st);
-      if (nb == 2) return launch_fwd<H, S, 2, true>(a, st);
-    } else {
-      if (nb == 1) return launch_fwd<H, S, 1, false>(a, st);
-      if (nb == 2) return launch_fwd<H, S, 2, false>(a, st);
-    }
-    return hipErrorInvalidValue;
-  }
+// Row/column-split backward (split 2: 4H lanes per layer, one sequence per
+// workgroup; the 4-slice row split is not built: a stack that fits it fits
+// the unit-group map).
+template <int H>
+Kernel bwd_rowsplit_kernel(int nb, int NL, int T) {
+  if (NL * 4 * H > 512) return no_kernel(hipErrorInvalidConfiguration);
+  if (nb != 1) return no_kernel(hipErrorInvalidValue);
+  return with_bools([&](auto XLDS) {
+    return kernel(lstm_small_bwd_kernel<H, 2, 1, XLDS>, 1, NL * 4 * H, with_x(sizeof(float) * NL * 6 * H, H, 1, T));
+  }, x_in_lds(H, 1, T));
 }
 
 template <int H>
-hipError_t dispatch_fwd(const PdrnnLstmSmallFwdArgs* a, int nb, int split, int save, hipStream_t st) {
-  if (a->cell == 1 && split != 1) return hipErrorInvalidConfiguration;  // GRU: gate-split map only
-  if (split == 1) {  // gate-split map (4 lanes per unit, one gate each)
-    if (a->NL * 4 * H > 512) return hipErrorInvalidConfiguration;
-
-    if (a->cell == 1) {
-      if (nb == 2) return save ? launch_fwd_gs_gru<H, 2, true>(a, st) : launch_fwd_gs_gru<H, 2, false>(a, st);
-      return save ? launch_fwd_gs_gru<H, 1, true>(a, st) : launch_fwd_gs_gru<H, 1, false>(a, st);
-    }
-    if (save) return nb == 2 ? launch_fwd_gs<H, 2, true>(a, st) : launch_fwd_gs<H, 1, true>(a, st);
-    return nb == 2 ? launch_fwd_gs<H, 2, false>(a, st) : launch_fwd_gs<H, 1, false>(a, st);
-  }
-  // (K splits of 4 / 8 lanes per unit are never the widest valid map -- a
-  // stack that fits them fits the gate-split map -- and are not built)
-  if (split == 2) return dispatch_fwd_s<H, 2>(a, nb, save, st);
-  return hipErrorInvalidValue;
-}
-
-template <int H, int S2>
-hipError_t dispatch_bwd_s(const PdrnnLstmSmallBwdArgs* a, int nb, hipStream_t st) {
-  if constexpr (!bwd_ok(H, S2)) {
-    return hipErrorInvalidValue;
-  } else {
-    if (a->NL * 2 * H * S2 > 512) return hipErrorInvalidConfiguration;
-    if (nb == 1) return launch_bwd<H, S2, 1>(a, st);
-    return hipErrorInvalidValue;
-  }
-}
-
-template <int H>
-hipError_t dispatch_bwd(const PdrnnLstmSmallBwdArgs* a, int nb, int split, hipStream_t st, int grid_hint) {
+hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, int nb, int split, int grid, hipStream_t st) {
   if (a->cell == 1 && (split != 1 || nb != 1)) return hipErrorInvalidConfiguration;
-  if (split == 1) {  // unit-group map, L lanes per unit (row slices of 4H/L)
-    if (a->cell == 1) {
-      if (a->NL * H * (H >= 64 ? 8 : 4) > 512) return hipErrorInvalidConfiguration;
-      if constexpr (H >= 64) return launch_bwd_gs_gru<H, 8>(a, st, grid_hint);
-      else return launch_bwd_gs_gru<H, 4>(a, st, grid_hint);
-    }
-    if (bwd_gs_lanes<H>(a->NL) == 8) {
-      if constexpr (H <= 32) {
-        switch (nb) {
-          case 1: return launch_bwd_gs<H, 8, 1>(a, st, grid_hint);
-          case 2: return launch_bwd_gs<H, 8, 2>(a, st, grid_hint);
-          case 3: return launch_bwd_gs<H, 8, 3>(a, st, grid_hint);
-          default: return hipErrorInvalidConfiguration;
-        }
-      }
-      if constexpr (H == 64) {
-        switch (nb) {
-          case 1: return launch_bwd_gs<H, 8, 1>(a, st, grid_hint);
-          default: return hipErrorInvalidConfiguration;
-        }
-      }
-    }
-    constexpr int L = 4;
-    if constexpr (H <= 32) {
-      if (a->NL * H * L > 512) return hipErrorInvalidConfiguration;
-      switch (nb) {
-        case 1: return launch_bwd_gs<H, L, 1>(a, st, grid_hint);
-        case 2: return launch_bwd_gs<H, L, 2>(a, st, grid_hint);
-        case 3: return launch_bwd_gs<H, L, 3>(a, st, grid_hint);
-        default: return hipErrorInvalidConfiguration;
-      }
-    }
-    return hipErrorInvalidConfiguration;
-  }
-  // (likewise the 4-slice row split: a stack that fits it fits the unit-group map)
-  if (split == 2) return dispatch_bwd_s<H, 2>(a, nb, st);
-  return hipErrorInvalidValue;
+  if (split != 1 && split != 2) return hipErrorInvalidValue;
+  const Kernel k = split == 1 ? bwd_gs_kernel<H>(a->cell, nb, a->NL, a->T, bwd_lean(a))
+                              : bwd_rowsplit_kernel<H>(nb, a->NL, a->T);
+  if (split == 2) grid = tiles(a->B, 1);
+  return launch(k, grid > 0 ? grid : persistent_grid(k, a->B), st, a);
 }
 
+// One-launch step (H <= 32): gate-split forward + head/CE + L = 4 unit-group
+// backward of sequence b in workgroup b.
 template <int H>
-hipError_t launch_step_gs(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b, hipStream_t st) {
+hipError_t launch_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b, hipStream_t st) {
   if (f->NL * 4 * H > 512 || f->B != b->B || f->T != b->T || f->NL != b->NL) return hipErrorInvalidConfiguration;
   if (!f->head_w || f->C > 16 || !bwd_lean(b)) return hipErrorInvalidValue;
-  const int grid = f->B;
-  const int block = f->NL * 4 * H;  // = NL * H * L with L = 4
-  const size_t lds_f = sizeof(float) * f->NL * 2 * (2 * H);
-  const size_t lds_b = bwd_gs_lds<H, 1>(f->NL);
-  const size_t lds = lds_f > lds_b ? lds_f : lds_b;
-  const size_t xbytes = sizeof(float) * (size_t)f->T * H;
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (f->cell == 1) {
-    if (xl) hipLaunchKernelGGL((lstm_small_step_gs_kernel<H, true, 1>), dim3(grid), dim3(block), lds + xbytes, st, *f, *b);
-    else hipLaunchKernelGGL((lstm_small_step_gs_kernel<H, false, 1>), dim3(grid), dim3(block), lds, st, *f, *b);
-  } else {
-    if (xl) hipLaunchKernelGGL((lstm_small_step_gs_kernel<H, true, 0>), dim3(grid), dim3(block), lds + xbytes, st, *f, *b);
-    else hipLaunchKernelGGL((lstm_small_step_gs_kernel<H, false, 0>), dim3(grid), dim3(block), lds, st, *f, *b);
-  }
-  return hipGetLastError();
+  const size_t lds_f = fwd_lds(H, 1, f->NL), lds_b = bwd_gs_lds(H, 1, f->NL);
+  const Kernel k = with_bools([&](auto XLDS, auto GRU) {
+    return kernel(lstm_small_step_gs_kernel<H, XLDS, GRU ? 1 : 0>, 1, f->NL * 4 * H,  // = NL * H * L with L = 4
+                  with_x(lds_f > lds_b ? lds_f : lds_b, H, 1, f->T));
+  }, x_in_lds(H, 1, f->T), f->cell == 1);
+  return launch(k, f->B, st, f, b);
 }
 
-// ---- deferred-dW backward (DWOUT) ----------------------------------------
+// Deferred-dW backward (DWOUT).  The instantiations without the LDS x image,
+// and H = 64 with two sequences, serve the residency queries only: the launch
+// refuses them.
 template <int H>
-constexpr int dwout_lanes() { return H >= 64 ? 8 : 4; }
-
-template <int H, int NB, bool XLDS, int CELL>
-int bwd_dwout_resident(int NL, size_t lds) {
-  constexpr int L = dwout_lanes<H>();
-  static thread_local int c_dev = -1, c_nl = -1, c_val = 0;
-  static thread_local size_t c_lds = 0;
-  int per_cu = 0, cus = 0, dev = 0;
-  hipGetDevice(&dev);
-  if (dev == c_dev && NL == c_nl && lds == c_lds) return c_val;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_small_bwd_dwout_kernel<H, L, NB, XLDS, CELL>,
-                                               NL * H * L, lds);
-  if (per_cu < 1) per_cu = 1;
-  if (cus < 1) cus = 1;
-  c_dev = dev; c_nl = NL; c_lds = lds; c_val = per_cu * cus;
-  return c_val;
-}
-
-template <int H, int NB>
-int bwd_dwout_cap(int NL, int T, int cell) {
-  const size_t lds = bwd_gs_lds<H, NB>(NL), xbytes = bwd_gs_xbytes<H, NB>(T);
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  return cell == 1 ? (xl ? bwd_dwout_resident<H, NB, true, 1>(NL, lds + xbytes)
-                         : bwd_dwout_resident<H, NB, false, 1>(NL, lds))
-                   : (xl ? bwd_dwout_resident<H, NB, true, 0>(NL, lds + xbytes)
-                         : bwd_dwout_resident<H, NB, false, 0>(NL, lds));
+Kernel dwout_kernel(int cell, int nb, int NL, int T) {
+  return with_int<1, 2>(nb, no_kernel(hipErrorInvalidValue), [&](auto nb_c) {
+    constexpr int NB = decltype(nb_c)::value, L = kUnitLanes<H>;
+    return with_bools([&](auto XLDS, auto GRU) {
+      return kernel(lstm_small_bwd_dwout_kernel<H, L, NB, XLDS, GRU ? 1 : 0>, NB, NL * H * L,
+                    with_x(bwd_gs_lds(H, NB, NL), H, NB, T));
+    }, x_in_lds(H, NB, T), cell == 1);
+  });
 }
 
 // Sequences per workgroup of the deferred-dW backward: 2 when pairing the
@@ -1813,8 +1578,8 @@ template <int H>
 int bwd_dwout_nb(int NL, int T, int B, int cell) {
   const int env = pdrnn_tune_int("dwout_nb", 0);  // per call: tests flip it in-process
   if (env == 1 || env == 2) return env;
-  if (H > 32 || NL * H * dwout_lanes<H>() > 512) return 1;
-  const int cap1 = bwd_dwout_cap<H, 1>(NL, T, cell), cap2 = bwd_dwout_cap<H, 2>(NL, T, cell);
+  if (H > 32 || NL * H * kUnitLanes<H> > 512) return 1;
+  const int cap1 = resident(dwout_kernel<H>(cell, 1, NL, T)), cap2 = resident(dwout_kernel<H>(cell, 2, NL, T));
   const int r1 = (B + cap1 - 1) / cap1, r2 = ((B + 1) / 2 + cap2 - 1) / cap2;
   return r2 < r1 ? 2 : 1;
 }
@@ -1826,36 +1591,22 @@ int bwd_dwout_nb(int NL, int T, int B, int cell) {
 // make each recurrence step cheaper.
 template <int H>
 int bwd_dwout_grid(int NL, int T, int B, int cell, int nb) {
-  const int cap = nb == 2 ? bwd_dwout_cap<H, 2>(NL, T, cell) : bwd_dwout_cap<H, 1>(NL, T, cell);
-  const int tiles = (B + nb - 1) / nb;
-  if (tiles <= cap) return tiles;
-  const int rounds = (tiles + cap - 1) / cap;
-  return (tiles + rounds - 1) / rounds;
-}
-
-template <int H, int NB>
-hipError_t launch_bwd_dwout_nb(const PdrnnLstmSmallBwdArgs* a, hipStream_t st, int grid) {
-  constexpr int L = dwout_lanes<H>();
-  const int block = a->NL * H * L;
-  const size_t lds = bwd_gs_lds<H, NB>(a->NL), xbytes = bwd_gs_xbytes<H, NB>(a->T);
-  const bool xl = xbytes <= (size_t)kXldsBytes;
-  if (!xl || !a->xg_out) return hipErrorInvalidConfiguration;  // x staged once per sequence (writes xg_out)
-  if (grid <= 0) grid = bwd_dwout_grid<H>(a->NL, a->T, a->B, a->cell, NB);
-  if (a->cell == 1) hipLaunchKernelGGL((lstm_small_bwd_dwout_kernel<H, L, NB, true, 1>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  else hipLaunchKernelGGL((lstm_small_bwd_dwout_kernel<H, L, NB, true, 0>), dim3(grid), dim3(block), lds + xbytes, st, *a);
-  return hipGetLastError();
+  const Kernel k = dwout_kernel<H>(cell, nb, NL, T);
+  if (k.err != hipSuccess) return -1;
+  const int cap = resident(k), t = tiles(B, nb);
+  if (t <= cap) return t;
+  const int rounds = (t + cap - 1) / cap;
+  return (t + rounds - 1) / rounds;
 }
 
 template <int H>
 hipError_t launch_bwd_dwout(const PdrnnLstmSmallBwdArgs* a, hipStream_t st, int grid, int nb) {
-  constexpr int L = dwout_lanes<H>();
-  if (a->NL * H * L > 512) return hipErrorInvalidConfiguration;
+  if (a->NL * H * kUnitLanes<H> > 512) return hipErrorInvalidConfiguration;
   if (!bwd_lean(a) || !a->dg_out || a->dg_st < 4 * H) return hipErrorInvalidValue;
-  if (nb == 2) {
-    if constexpr (H <= 32) return launch_bwd_dwout_nb<H, 2>(a, st, grid);
-    return hipErrorInvalidConfiguration;
-  }
-  return launch_bwd_dwout_nb<H, 1>(a, st, grid);
+  // x is staged once per sequence (and written to xg_out): it has to fit LDS
+  if ((nb == 2 && H > 32) || !x_in_lds(H, nb, a->T) || !a->xg_out) return hipErrorInvalidConfiguration;
+  if (grid <= 0) grid = bwd_dwout_grid<H>(a->NL, a->T, a->B, a->cell, nb);
+  return launch(dwout_kernel<H>(a->cell, nb, a->NL, a->T), grid, st, a);
 }
 
 }  // namespace
@@ -1872,40 +1623,25 @@ int pdrnn_lstm_small_dwout_ok(int H, int NL, int T) {
   const int mode = !pdrnn_tune_str("dwout", e, (int)sizeof(e)) ? 1 : (e[0] == '0' ? 0 : (strcmp(e, "force") == 0 ? 2 : 1));
   if (mode == 0 || T < 4 || NL < 1 || NL > PDRNN_MAX_LAYERS) return 0;
   if (H != 16 && H != 32 && H != 64) return 0;
-  if ((size_t)T * H * sizeof(float) > (size_t)pdrnn::kXldsBytes) return 0;  // LDS-resident x only
+  if (!pdrnn::x_in_lds(H, 1, T)) return 0;  // LDS-resident x only
   return NL * H * (H >= 64 ? 8 : 4) <= 512 ? mode : 0;
 }
 
+// (LSTM and GRU instantiations share the register budget -- same VGPR class;
+// the LSTM's is the one queried)
 int pdrnn_lstm_small_bwd_dwout_nb(int H, int NL, int T, int B) {
-  // LSTM and GRU instantiations share the register budget (same VGPR class);
-  // the LSTM's is the one queried
-  switch (H) {
-    case 16: return pdrnn::bwd_dwout_nb<16>(NL, T, B, 0);
-    case 32: return pdrnn::bwd_dwout_nb<32>(NL, T, B, 0);
-    case 64: return pdrnn::bwd_dwout_nb<64>(NL, T, B, 0);
-    default: return -1;
-  }
+  return pdrnn::with_hidden(H, -1, [&](auto h) { return pdrnn::bwd_dwout_nb<h>(NL, T, B, 0); });
 }
-
 int pdrnn_lstm_small_bwd_dwout_grid(int H, int NL, int T, int B, int nb) {
-  switch (H) {
-    case 16: return pdrnn::bwd_dwout_grid<16>(NL, T, B, 0, nb);
-    case 32: return pdrnn::bwd_dwout_grid<32>(NL, T, B, 0, nb);
-    case 64: return pdrnn::bwd_dwout_grid<64>(NL, T, B, 0, nb);
-    default: return -1;
-  }
+  return pdrnn::with_hidden(H, -1, [&](auto h) { return pdrnn::bwd_dwout_grid<h>(NL, T, B, 0, nb); });
 }
 
 hipError_t pdrnn_lstm_small_bwd_dwout(const PdrnnLstmSmallBwdArgs* a, int H, int grid, int nb, hipStream_t stream) {
-  if (a->x_bf16 && (size_t)a->T * H * sizeof(float) * (nb > 1 ? nb : 1) > (size_t)pdrnn::kXldsBytes)
-    return hipErrorInvalidConfiguration;
+  if (a->x_bf16 && !pdrnn::x_in_lds(H, nb > 1 ? nb : 1, a->T)) return hipErrorInvalidConfiguration;
   if (nb != 1 && nb != 2) return hipErrorInvalidValue;
-  switch (H) {
-    case 16: return pdrnn::launch_bwd_dwout<16>(a, stream, grid, nb);
-    case 32: return pdrnn::launch_bwd_dwout<32>(a, stream, grid, nb);
-    case 64: return pdrnn::launch_bwd_dwout<64>(a, stream, grid, nb);
-    default: return hipErrorInvalidValue;
-  }
+  return pdrnn::with_hidden(H, hipErrorInvalidValue, [&](auto h) {
+    return pdrnn::launch_bwd_dwout<h>(a, stream, grid, nb);
+  });
 }
 
 // 1 when the fused one-launch step covers (H, NL, B, launch config): the
@@ -1914,29 +1650,23 @@ hipError_t pdrnn_lstm_small_bwd_dwout(const PdrnnLstmSmallBwdArgs* a, int H, int
 int pdrnn_lstm_small_step_ok(int H, int NL, int B, int nb_fwd, int split_fwd, int nb_bwd, int split_bwd,
                              int gridb) {
   if ((H != 16 && H != 32) || nb_fwd != 1 || split_fwd != 1 || nb_bwd != 1 || split_bwd != 1) return 0;
-  if (NL * 4 * H > 512 || gridb != B) return 0;
-  const int lanes = H == 16 ? pdrnn::bwd_gs_lanes<16>(NL) : pdrnn::bwd_gs_lanes<32>(NL);
-  return lanes == 4 ? 1 : 0;
+  return NL * 4 * H <= 512 && gridb == B;
 }
 
 // Fused forward + head/CE + BPTT launch of the latency regime (see
 // lstm_small_step_gs_kernel); H in {16, 32}.
 hipError_t pdrnn_lstm_small_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b, int H,
                                  hipStream_t stream) {
-  if (f->x_bf16 && (size_t)f->T * H * sizeof(float) > (size_t)pdrnn::kXldsBytes) return hipErrorInvalidConfiguration;
-  switch (H) {
-    case 16: return pdrnn::launch_step_gs<16>(f, b, stream);
-    case 32: return pdrnn::launch_step_gs<32>(f, b, stream);
-    default: return hipErrorInvalidValue;
-  }
+  if (f->x_bf16 && !pdrnn::x_in_lds(H, 1, f->T)) return hipErrorInvalidConfiguration;
+  return pdrnn::with_int<16, 32>(H, hipErrorInvalidValue, [&](auto h) { return pdrnn::launch_step<h>(f, b, stream); });
 }
 
+// H in {16, 32}: 4 lanes per unit in both passes, up to 4 layers per 512-lane
+// workgroup.  H = 64: the backward's 8 lanes per unit fill it with one layer.
 int pdrnn_lstm_small_supported(int H, int I, int NL) {
-  const bool h_ok = H == 16 || H == 32 || H == 64;
-  if (!h_ok || I < 1 || I > H || NL < 1 || NL > PDRNN_MAX_LAYERS) return 0;
-  const int s_min = H == 32 ? 2 : 4;   // smallest valid forward split
-  const int s2_min = H == 64 ? 4 : 2;  // smallest valid backward split
-  return (NL * H * s_min <= 512 && NL * 2 * H * s2_min <= 512) ? 1 : 0;
+  if (I < 1 || I > H || NL < 1) return 0;
+  if (H == 16 || H == 32) return NL <= PDRNN_MAX_LAYERS;
+  return H == 64 && NL == 1;
 }
 
 // Largest split whose workgroup fits: more lanes per unit = shorter
@@ -1953,118 +1683,33 @@ int pdrnn_lstm_small_max_split(int H, int NL, int backward) {
   return 0;
 }
 
-int pdrnn_lstm_small_grid(int H, int B, int nb) {
-  (void)H;
-  return (B + nb - 1) / nb;
-}
-
 hipError_t pdrnn_lstm_small_fwd(const PdrnnLstmSmallFwdArgs* a, int H, int nb, int split, int save,
                                 hipStream_t stream) {
   // bf16 inputs are widened while staging x into LDS: needs the LDS-resident x path
-  if (a->x_bf16 && (size_t)a->T * H * sizeof(float) * (nb > 1 ? nb : 1) > (size_t)pdrnn::kXldsBytes)
-    return hipErrorInvalidConfiguration;
-  switch (H) {
-    case 16: return pdrnn::dispatch_fwd<16>(a, nb, split, save, stream);
-    case 32: return pdrnn::dispatch_fwd<32>(a, nb, split, save, stream);
-    case 64: return pdrnn::dispatch_fwd<64>(a, nb, split, save, stream);
-    default: return hipErrorInvalidValue;
-  }
+  if (a->x_bf16 && !pdrnn::x_in_lds(H, nb > 1 ? nb : 1, a->T)) return hipErrorInvalidConfiguration;
+  return pdrnn::with_hidden(H, hipErrorInvalidValue, [&](auto h) {
+    const pdrnn::Kernel k = pdrnn::fwd_kernel<h>(a, nb, split, save != 0);
+    return pdrnn::launch(k, pdrnn::tiles(a->B, k.nb), stream, a);
+  });
 }
 
 hipError_t pdrnn_lstm_small_bwd(const PdrnnLstmSmallBwdArgs* a, int H, int nb, int split, int grid,
                                 hipStream_t stream) {
-  if (a->x_bf16 && (split != 1 || (size_t)a->T * H * sizeof(float) * (nb > 1 ? nb : 1) > (size_t)pdrnn::kXldsBytes))
-    return hipErrorInvalidConfiguration;
-  switch (H) {
-    case 16: return pdrnn::dispatch_bwd<16>(a, nb, split, stream, grid);
-    case 32: return pdrnn::dispatch_bwd<32>(a, nb, split, stream, grid);
-    case 64: return pdrnn::dispatch_bwd<64>(a, nb, split, stream, grid);
-    default: return hipErrorInvalidValue;
-  }
+  if (a->x_bf16 && (split != 1 || !pdrnn::x_in_lds(H, nb > 1 ? nb : 1, a->T))) return hipErrorInvalidConfiguration;
+  return pdrnn::with_hidden(H, hipErrorInvalidValue, [&](auto h) {
+    return pdrnn::launch_bwd<h>(a, nb, split, grid, stream);
+  });
 }
 
-// Slab rows (= grid) the backward will use for (H, NL, T, B, split).
+// Slab rows (= grid) the backward will use for (H, NL, T, B, split).  The
+// general LSTM instantiation is the one queried whatever the launch will be
+// (GRU, lean contract): the slab rows, and with them the order in which the
+// gradients are summed, depend on neither.
 int pdrnn_lstm_small_bwd_grid(int H, int NL, int T, int B, int nb, int split) {
   if (split != 1) return (B + nb - 1) / nb;
-  PdrnnLstmSmallBwdArgs a{};
-  a.NL = NL; a.T = T; a.B = B;
-#define BWD_GRID_CASE(HH, LL)                                   \
-  switch (nb) {                                                  \
-    case 1: return pdrnn::bwd_gs_grid<HH, LL, 1>(&a);            \
-    case 2: return pdrnn::bwd_gs_grid<HH, LL, 2>(&a);            \
-    case 3: return pdrnn::bwd_gs_grid<HH, LL, 3>(&a);            \
-    default: return -1;                                          \
-  }
-  switch (H) {
-    case 16:
-      if (pdrnn::bwd_gs_lanes<16>(NL) == 8) { BWD_GRID_CASE(16, 8) }
-      BWD_GRID_CASE(16, 4)
-    case 32:
-      if (pdrnn::bwd_gs_lanes<32>(NL) == 8) { BWD_GRID_CASE(32, 8) }
-      BWD_GRID_CASE(32, 4)
-    case 64:
-      if (nb != 1) return -1;
-      return pdrnn::bwd_gs_grid<64, 8, 1>(&a);
-    default: return -1;
-  }
-#undef BWD_GRID_CASE
-}
-
-hipError_t pdrnn_slab_reduce(const float* slab, int64_t rows, int64_t P, float* out, float beta,
-                             float* work, int split, hipStream_t stream) {
-  if (split < 1) split = 1;
-  if (split > 64) split = 64;
-  if (split > rows) split = (int)rows > 0 ? (int)rows : 1;
-  const int threads = 256;
-  dim3 g1((unsigned)((P + threads - 1) / threads), (unsigned)split);
-  hipLaunchKernelGGL(pdrnn::slab_reduce_pass1, g1, dim3(threads), 0, stream, slab, rows, P, work, split);
-  PDRNN_HIP_CHECK(hipGetLastError());
-  dim3 g2((unsigned)((P + threads - 1) / threads));
-  hipLaunchKernelGGL(pdrnn::slab_reduce_pass2, g2, dim3(threads), 0, stream, work, P, split, out, beta);
-  return hipGetLastError();
-}
-
-hipError_t pdrnn_slab_reduce2(const float* slab, int64_t rows, int64_t P, int64_t P_a, float* out_a,
-                              float* out_b, float* work, int split, hipStream_t stream) {
-  if (split < 1) split = 1;
-  if (split > 64) split = 64;
-  if (split > rows) split = (int)rows > 0 ? (int)rows : 1;
-  const int threads = 256;
-  dim3 g1((unsigned)((P + threads - 1) / threads), (unsigned)split);
-  hipLaunchKernelGGL(pdrnn::slab_reduce_pass1, g1, dim3(threads), 0, stream, slab, rows, P, work, split);
-  PDRNN_HIP_CHECK(hipGetLastError());
-  dim3 g2((unsigned)((P + threads - 1) / threads));
-  hipLaunchKernelGGL(pdrnn::slab_reduce_pass2_split, g2, dim3(threads), 0, stream, work, P, P_a, split, out_a, out_b);
-  return hipGetLastError();
-}
-
-hipError_t pdrnn_slab2_reduce_pass1(const float* A, int64_t rowsA, int64_t PA, const float* Bs, int64_t rowsB,
-                                   int64_t PB, float* work, int split, const int* colmap, int64_t ldA,
-                                   hipStream_t stream) {
-  if (split < 1) split = 1;
-  if (split > 64) split = 64;
-  const int64_t P = PA + PB;
-  const int threads = 256;
-  dim3 g1((unsigned)((P + threads - 1) / threads), (unsigned)split);
-  hipLaunchKernelGGL(pdrnn::slab2_reduce_pass1, g1, dim3(threads), 0, stream, A, rowsA, PA, Bs, rowsB, PB, work, split,
-                     colmap, colmap ? ldA : PA);
-  return hipGetLastError();
-}
-
-hipError_t pdrnn_slab2_reduce(const float* A, int64_t rowsA, int64_t PA, const float* Bs, int64_t rowsB, int64_t PB,
-                              int64_t n_out, float* out, float* out_tail, float* work, int split, const int* colmap,
-                              int64_t ldA, hipStream_t stream) {
-  if (split < 1) split = 1;
-  if (split > 64) split = 64;
-  const int64_t P = PA + PB;
-  const int threads = 256;
-  dim3 g1((unsigned)((P + threads - 1) / threads), (unsigned)split);
-  hipLaunchKernelGGL(pdrnn::slab2_reduce_pass1, g1, dim3(threads), 0, stream, A, rowsA, PA, Bs, rowsB, PB, work, split,
-                     colmap, colmap ? ldA : PA);
-  PDRNN_HIP_CHECK(hipGetLastError());
-  dim3 g2((unsigned)((P + threads - 1) / threads));
-  hipLaunchKernelGGL(pdrnn::slab_reduce_pass2_split, g2, dim3(threads), 0, stream, work, P, n_out, split, out, out_tail);
-  return hipGetLastError();
+  return pdrnn::with_hidden(H, -1, [&](auto h) {
+    return pdrnn::persistent_grid(pdrnn::bwd_gs_kernel<h>(0, nb, NL, T, false), B);
+  });
 }
 
 }  // extern "C"

@@ -30,7 +30,8 @@ def small_launch_config(batch: int, hidden: int, num_layers: int = 2) -> Tuple[i
     ``split``: lanes per hidden unit (more lanes = shorter per-timestep
     critical path).  Small batches are latency-bound -> widest split, one
     sequence per workgroup.  Overrides (for sweeps, PDRNN_TUNE): nb_fwd,
-    split_fwd, nb_bwd, split_bwd."""
+    split_fwd, nb_bwd, split_bwd.  What the fused training step makes of them
+    (which of its five paths, on which grids): ``_C.lstm_head_step_plan``."""
     nb_fwd = tune_int("nb_fwd", 0)
     nb_bwd = tune_int("nb_bwd", 0)
     sp_fwd = tune_int("split_fwd", 0)

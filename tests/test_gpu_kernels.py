@@ -42,6 +42,57 @@ def test_lstm_small_fwd_bwd_matches_torch(H, NL, I, B, T):
         assert err / scale < 2e-4, (err, scale)
 
 
+# Shortest sequences whose x no longer fits the kernels' 48 KiB LDS image
+# (NB * T * H * 4 > 49152): layer 0 then streams x from global memory.  The
+# third shape leaves LDS only with two sequences per forward workgroup.
+_STREAMED_X = [(64, 1, 40, 3, 193, 1), (32, 2, 9, 3, 385, 1), (32, 2, 9, 4, 193, 2)]
+
+
+@pytest.mark.parametrize("H,NL,I,B,T,nb_fwd", _STREAMED_X)
+def test_lstm_small_streamed_x_matches_torch(H, NL, I, B, T, nb_fwd, monkeypatch):
+    """test_lstm_small_fwd_bwd_matches_torch past the LDS-resident x: training
+    (saving) and no_grad (inference) forward, and the backward (8 lanes per
+    unit at H = 64, 4 at H = 32)."""
+    from _tune import set_tune
+    from pytorch_distributed_rnn_amd.ops.lstm import lstm_forward
+    assert nb_fwd * T * H * 4 > 48 * 1024
+    set_tune(monkeypatch, nb_fwd=str(nb_fwd))
+    ref = _make_lstm(I, H, NL).double()
+    x = torch.randn(B, T, I, dtype=torch.float64)
+    out_ref, (hn_ref, cn_ref) = ref(x)
+    g_out = torch.randn_like(out_ref)
+    g_hn = torch.randn_like(hn_ref)
+    (out_ref * g_out).sum().add_((hn_ref * g_hn).sum()).backward()
+
+    dev = torch.device("cuda")
+    ws = [p.detach().float().to(dev).requires_grad_() for p in ref.parameters()]
+    xg = x.float().to(dev)
+    with torch.no_grad():
+        res_infer = lstm_forward(xg, ws, hidden=H, num_layers=NL, batch_first=True)
+    out, hn, cn = lstm_forward(xg, ws, hidden=H, num_layers=NL, batch_first=True)
+    for o, h, c in (res_infer, (out, hn, cn)):
+        assert torch.allclose(o.double().cpu(), out_ref, atol=2e-5, rtol=1e-4)
+        assert torch.allclose(h.double().cpu(), hn_ref, atol=2e-5, rtol=1e-4)
+        assert torch.allclose(c.double().cpu(), cn_ref, atol=2e-5, rtol=1e-4)
+    loss = (out * g_out.float().to(dev)).sum() + (hn * g_hn.float().to(dev)).sum()
+    loss.backward()
+    for w, p in zip(ws, ref.parameters()):
+        scale = p.grad.abs().max().item() + 1e-6
+        err = (w.grad.double().cpu() - p.grad).abs().max().item()
+        assert err / scale < 2e-4, (err, scale)
+
+
+def test_lstm_small_supported_table():
+    """The fused small-H stack covers H in {16, 32} with 1..4 layers and H = 64
+    with one layer, inputs 1..H wide; nothing else."""
+    mod = _C()
+    for H in (8, 16, 32, 64, 128):
+        for NL in range(1, 6):
+            for I in (1, H, H + 1):
+                expect = I <= H and ((H in (16, 32) and NL <= 4) or (H == 64 and NL == 1))
+                assert mod.lstm_small_supported(H, I, NL) == expect, (H, I, NL)
+
+
 def test_lstm_small_seq_first_and_states():
     from pytorch_distributed_rnn_amd.ops.lstm import lstm_forward
     H, NL, I, B, T = 32, 2, 9, 5, 11
@@ -240,6 +291,44 @@ def test_fused_gru_matches_torch(H, NL, I, B, T, bf):
     xb, h0b = x.double().clone().requires_grad_(True), h0.double().clone().requires_grad_(True)
     out, hn = m(xa, h0a)
     out_r, hn_r = ref(xb, h0b)
+    torch.testing.assert_close(out.double(), out_r, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(hn.double(), hn_r, rtol=1e-4, atol=1e-4)
+    g = torch.randn_like(out_r)
+    ((out.double() * g).sum() + hn.double().sum()).backward()
+    ((out_r * g).sum() + hn_r.sum()).backward()
+    torch.testing.assert_close(xa.grad.double(), xb.grad, rtol=1e-3, atol=1e-4)
+    torch.testing.assert_close(h0a.grad.double(), h0b.grad, rtol=1e-3, atol=1e-4)
+    for (n, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
+        torch.testing.assert_close(p.grad.double(), q.grad, rtol=1e-3, atol=2e-4, msg=n)
+
+
+@pytest.mark.parametrize("H,NL,I,B,T,nb_fwd", _STREAMED_X)
+def test_fused_gru_streamed_x_matches_torch(H, NL, I, B, T, nb_fwd, monkeypatch):
+    """test_fused_gru_matches_torch past the LDS-resident x.  The GRU operator
+    always saves for the backward and runs one sequence per workgroup: the
+    inference forward is called on the binding, and two sequences per
+    workgroup are forced on the operator's forward launch."""
+    from pytorch_distributed_rnn_amd.models.rnn import GRU
+    from pytorch_distributed_rnn_amd.ops.gru_fused import _pack
+    torch.manual_seed(11)
+    m = GRU(I, H, NL, batch_first=True).cuda()
+    ref = torch.nn.GRU(I, H, NL, batch_first=True).cuda().double()
+    with torch.no_grad():
+        for (n, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
+            q.copy_(p.double())
+    x = torch.randn(B, T, I, device="cuda")
+    h0 = torch.randn(NL, B, H, device="cuda")
+    xa, h0a = x.clone().requires_grad_(True), h0.clone().requires_grad_(True)
+    xb, h0b = x.double().clone().requires_grad_(True), h0.double().clone().requires_grad_(True)
+    out_r, hn_r = ref(xb, h0b)
+    mod = _C()
+    fwd = mod.lstm_small_fwd
+    packed = _pack([p.detach() for p in m.parameters()], NL, H, x)
+    out_i, hn_i, _, _ = fwd(x, None, packed, h0, None, H, NL, True, False, True, nb_fwd, 1, cell=1)
+    torch.testing.assert_close(out_i.double(), out_r, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(hn_i.double(), hn_r, rtol=1e-4, atol=1e-4)
+    monkeypatch.setattr(mod, "lstm_small_fwd", lambda *a, **k: fwd(*a[:10], nb_fwd, *a[11:], **k))
+    out, hn = m(xa, h0a)
     torch.testing.assert_close(out.double(), out_r, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(hn.double(), hn_r, rtol=1e-4, atol=1e-4)
     g = torch.randn_like(out_r)

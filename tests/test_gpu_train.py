@@ -67,6 +67,93 @@ def test_one_launch_step_shapes_match_autograd(cell, hidden, layers):
         assert torch.allclose(p, q, atol=2e-5, rtol=1e-4), k
 
 
+@pytest.mark.parametrize("cell", ["lstm", "gru"])
+def test_one_launch_step_streamed_x_matches_autograd(cell, monkeypatch):
+    """The one-launch step past the LDS-resident x (T = 400: T * H * 4 > 48
+    KiB, layer 0 streams x from global memory) equals the autograd step."""
+    from pytorch_distributed_rnn_amd import _ext
+    from pytorch_distributed_rnn_amd.data.motion import synthetic_motion
+    from pytorch_distributed_rnn_amd.models.motion import MotionModel
+    from pytorch_distributed_rnn_amd.train.trainer import Trainer
+    monkeypatch.setenv("PDRNN_SW", "0")
+    set_tune(monkeypatch, dwout=None)
+    torch.manual_seed(1)
+    train, _, _ = synthetic_motion(n_train=64, n_validation=2, n_test=2, seq_length=400, seed=5)
+    m1 = MotionModel(9, 32, 2, 6, cell=cell)
+    m2 = copy.deepcopy(m1)
+    t1 = Trainer(m1, train, batch_size=32, learning_rate=2.5e-3, device=torch.device("cuda"))
+    t2 = Trainer(m2, train, batch_size=32, learning_rate=2.5e-3, device=torch.device("cuda"))
+    t2._fused = None
+    assert t1._fused_step() is not None, "fused step not selected on GPU"
+    mod = _ext.native(torch.device("cuda", 0))
+    assert mod.lstm_small_step_one_launch(32, 2, 400, 32, 1, 0, 1, 0)
+    for x1, x2 in zip(list(t1.train_loader), list(t2.train_loader)):
+        s1, _ = t1.train_batch(x1)
+        s2, _ = t2.train_batch(x2)
+        assert abs(float(s1[0]) - float(s2[0])) < 1e-5
+        assert int(s1[2]) == int(s2[2])
+    for (k, p), q in zip(m1.named_parameters(), m2.parameters()):
+        assert torch.allclose(p, q, atol=2e-5, rtol=1e-4), k
+
+
+def test_multi_sequence_backward_streamed_x_gradients_match_fp64(monkeypatch):
+    """Two sequences per workgroup of the register-dW backward at T = 193: the
+    pair's x (2 * T * H * 4 > 48 KiB) is streamed from global memory.  Gradients
+    before Adam against fp64 autograd, each within 2e-4 of the parameter's
+    largest gradient (the bound of test_lstm_small_fwd_bwd_matches_torch)."""
+    from pytorch_distributed_rnn_amd.data.motion import synthetic_motion
+    from pytorch_distributed_rnn_amd.models.motion import MotionModel
+    monkeypatch.setenv("PDRNN_SW", "0")
+    set_tune(monkeypatch, nb_bwd="2", dwout=None)
+    torch.manual_seed(7)
+    train, _, _ = synthetic_motion(n_train=4, n_validation=2, n_test=2, seq_length=193, seed=8)
+    _fp64_check(MotionModel(9, 32, 2, 6), train, 4, tol=2e-4)
+
+
+def test_step_plan_agrees_with_selection_queries(monkeypatch):
+    """lstm_head_step_plan is the decision lstm_head_train_step itself runs
+    on: at the shapes of the selection tests in this file it agrees with the
+    query bindings (which ask it about the gate-split / K-split family), and
+    names the expected one of the five paths."""
+    from pytorch_distributed_rnn_amd import _ext
+    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    mod = _ext.native(torch.device("cuda", 0))
+    H, I, NL, T = 32, 9, 2, 128
+
+    def plan(B, **kw):
+        nb_f, sp_f, _, sp_b = small_launch_config(B, H, NL)
+        p = mod.lstm_head_step_plan(H, I, NL, T, B, nb_fwd=nb_f, split_fwd=sp_f, nb_bwd=fused_bwd_nb(B, H, NL),
+                                    split_bwd=sp_b, **kw)
+        if not p["sw"]:
+            assert p["one_launch"] == mod.lstm_small_step_one_launch(H, NL, T, B, nb_f, sp_f, fused_bwd_nb(B, H, NL),
+                                                                     sp_b), B
+            assert p["dwout"] == mod.lstm_small_step_deferred_dw(H, NL, T, B), B
+            if p["dwout"]:
+                assert (p["nb_dw"], p["grid_dw"]) == mod.lstm_small_dwout_geometry(H, NL, T, B), B
+        return p
+
+    monkeypatch.delenv("PDRNN_SW", raising=False)
+    set_tune(monkeypatch, dwout=None, dwout_nb=None, nb_bwd=None, sw_mode=None, sw_bwd_mode=None)
+    for B, path in ((96, "one_launch"), (180, "one_launch"), (1440, "deferred_dw")):
+        assert plan(B, sw=0, stamps=False)["path"] == path, B
+    for B, path in ((96, "sw_one_launch"), (180, "sw_one_launch"), (1440, "sw_two_launch")):
+        p = plan(B)  # switches from the environment: the sequence-in-wave kernels
+        assert p["path"] == path and p["sw"] and p["dwout"], (B, p)
+        assert p["sw_step"] == mod.lstm_sw_step_ok(NL, B, T), B
+    p = plan(1440, sw=0)
+    assert (p["nb_dw"], p["grid_dw"]) == (2, 720) and p["slab_rows"] > 0, p
+    monkeypatch.setenv("PDRNN_SW", "2")  # sequence-in-wave, forward and BPTT launched apart
+    assert plan(180)["path"] == "sw_two_launch"
+    monkeypatch.setenv("PDRNN_SW", "0")
+    for B in (96, 180, 1440):
+        assert plan(B) == plan(B, sw=0, stamps=False), B
+    set_tune(monkeypatch, dwout="0")
+    p = plan(1440)
+    assert p["path"] == "register_dw" and p["slab_rows"] == p["gridb"] < 1440, p
+    set_tune(monkeypatch, dwout="force")
+    assert plan(96)["path"] == "deferred_dw"
+
+
 def test_one_launch_step_selected_in_latency_regime():
     """B <= one resident round: forward + head/CE + BPTT run as one launch
     (the B=96 runs of test_fused_step_matches_autograd go through it); the
