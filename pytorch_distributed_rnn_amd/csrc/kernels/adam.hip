@@ -7,7 +7,9 @@
 // optimizer step is a single streaming launch (16 B per lane, grid-stride).
 // The update follows torch.optim.Adam's single-tensor formula term by term
 // (lerp for exp_avg, addcmul for exp_avg_sq, sqrt(v)/sqrt(bc2)+eps,
-// addcdiv by lr/bc1).  `grad_scale` folds the 1/world average of a sum
+// addcdiv by lr/bc1), except that 1 - beta is formed in fp32 from the fp32
+// beta (torch forms it in double and then rounds: ~3e-5 relative in
+// exp_avg_sq at beta2 = 0.999).  `grad_scale` folds the 1/world average of a sum
 // all-reduce into the read of the gradient.
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"

@@ -119,13 +119,16 @@ __global__ void __launch_bounds__(256) xent_finalize_kernel(const float* partial
   }
 }
 
-// dst = src * (grad_out[0] / stats[1])
+// dst = src * (grad_out[0] / stats[1]); no valid row (stats[1] == 0): the
+// gradient is zero, as F.cross_entropy's is (src is all 0: 0 * inf otherwise)
 // OD: output 0 bf16, 1 fp16, 2 fp32 -- a 16-bit head takes its logits
-// gradient in its own dtype straight from here (no separate cast dispatch)
+// gradient in its own dtype straight from here (no separate cast dispatch).
+// The fp16 writer compiles to one v_fma_mixlo_f16: the product is rounded
+// once, to fp16 (the bf16 writer rounds the fp32 product)
 template <int OD>
 __global__ void xent_bwd_kernel(const float* __restrict__ src, const float* grad_out, const float* stats,
                                 void* __restrict__ dst, int64_t n) {
-  const float scale = grad_out[0] / stats[1];
+  const float scale = stats[1] != 0.f ? grad_out[0] / stats[1] : 0.f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float v = src[i] * scale;

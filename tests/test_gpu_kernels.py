@@ -147,7 +147,8 @@ def test_xent_matches_torch(N, C):
     valid = labels != -100
     assert stats[1].item() == valid.sum().item()
     assert stats[2].item() == ((logits.argmax(1) == labels) & valid).sum().item()
-    assert torch.allclose(lg.grad.double().cpu(), lr.grad, atol=1e-7)
+    # as grad * n_valid (softmax - onehot, of order 1): the same bound at every N
+    assert ((lg.grad.double().cpu() - lr.grad) * valid.sum()).abs().max().item() <= 2e-6
 
 
 def test_fused_adam_matches_torch():
