@@ -21,6 +21,8 @@ if [ "$1" = build ]; then
     fi
   done
   /opt/rocm/bin/hipcc -c $FL bench/sw_probe.cpp -o $OUT/sw_probe.o 2>/dev/null &
+  # (the kernels' PDRNN_TUNE reader)
+  /opt/rocm/bin/hipcc -c $FL pytorch_distributed_rnn_amd/csrc/runtime/tune.cpp -o $OUT/tune.o 2>/dev/null &
   wait
   /opt/rocm/bin/hipcc --offload-arch=gfx950 $OUT/*.o -o $OUT/${PROBE_NAME:-sw_probe}
   echo built $OUT/${PROBE_NAME:-sw_probe}

@@ -326,6 +326,35 @@ std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx,
   return {out, hn, cn, act};
 }
 
+// The sequence-in-wave forward (lstm_sw.hip) on its own, in the wave map
+// `mode`: {hseq [NL,B,T,H], act [NL,B,T,5,H], hn, cn}.  The train step runs
+// the same launch with the head fused in; this entry lets a test compare one
+// map's saved activations against another's.
+std::vector<Tensor> lstm_sw_fwd(const Tensor& x, const std::vector<Tensor>& w, int64_t H, int64_t NL, int64_t mode,
+                                int64_t cell, bool round_bf16) {
+  CHECK_HIP_TENSOR(x);
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "x must be float32 or bfloat16");
+  TORCH_CHECK(x.dim() == 3 && x.is_contiguous(), "x must be a contiguous [B, T, I]");
+  const c10::DeviceGuard guard(x.device());
+  const int64_t I = x.size(2);
+  bool has_bias = false;
+  check_stack(w, NL, H, I, has_bias);
+  PdrnnLstmSmallFwdArgs a{};
+  set_input(a, x, optional<Tensor>(), true);
+  set_weights(a, w, NL);
+  const int64_t B = a.B, T = a.T;
+  TORCH_CHECK(B > 0 && T > 0 && pdrnn_lstm_sw_ok((int)H, (int)I, (int)NL, (int)cell) == 1 &&
+              pdrnn_lstm_sw_fits((int)NL, (int)B, (int)T) == 1, "sequence-in-wave forward: unsupported shape");
+  auto opts = x.options().dtype(at::kFloat);
+  Tensor hseq = at::empty({NL, B, T, H}, opts), act = at::empty({NL, B, T, 5, H}, opts);
+  Tensor hn = at::empty({NL, B, H}, opts), cn = at::empty({NL, B, H}, opts);
+  a.hseq = hseq.data_ptr<float>(); a.act = act.data_ptr<float>();
+  a.hn = hn.data_ptr<float>(); a.cn = cn.data_ptr<float>();
+  a.NL = (int)NL; a.cell = (int)cell; a.w_bf16 = round_bf16 ? 1 : 0;
+  HIP_LAUNCH_CHECK(pdrnn_lstm_sw_fwd(&a, (int)mode, cur_stream()));
+  return {hseq, act, hn, cn};
+}
+
 // Returns {dparams_flat[P] (nn.LSTM parameter order), dx, dh0, dc0}.
 std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx, const std::vector<Tensor>& w,
                                    const optional<Tensor>& h0, const optional<Tensor>& c0, const Tensor& hseq,
@@ -480,6 +509,7 @@ HeadStepPlan plan_head_step(const HeadStepShape& s) {
     p.sw_fmode = pdrnn_lstm_sw_mode(NL, B, 0);
     p.sw_bmode = pdrnn_lstm_sw_mode(NL, B, 1);
     if (p.sw_bmode == 4 && T % 4) p.sw_bmode = 2;  // register dW: whole 4-step K steps
+    if (p.sw_fmode == 8 && !pdrnn_lstm_sw_fwd8_ok(NL, T)) p.sw_fmode = 6;  // whole 16-step chunks, six workgroups per CU
     // sequences per workgroup: two in modes 1 / 3 (mode 5, the four-wave forward, runs one)
     p.sw_fnb = pdrnn_lstm_sw_nb(p.sw_fmode);
     p.sw_bnb = pdrnn_lstm_sw_nb(p.sw_bmode);
@@ -1719,8 +1749,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "every act / hseq row of this batch fits the sequence-in-wave kernels' 2 GiB buffer descriptor");
   m.def("lstm_sw_mode", [](int64_t NL, int64_t B, bool backward) { return pdrnn_lstm_sw_mode((int)NL, (int)B, backward ? 1 : 0); },
         "wave map of the sequence-in-wave kernels for B sequences (0/1: a wave per 1/2 sequences, 2/3: a wave "
-        "per layer of 1/2 sequences, 6: mode 2 at three waves per SIMD, forward only)",
+        "per layer of 1/2 sequences, 6: mode 2 at three waves per SIMD, forward only; 8: mode 6 with layer 1's "
+        "input projection on the matrix cores per 16-step chunk, the same bits, forward only)",
         py::arg("NL"), py::arg("B"), py::arg("backward") = false);
+  m.def("lstm_sw_fwd", &lstm_sw_fwd, "sequence-in-wave stack forward in one wave map -> (hseq, act, hn, cn)",
+        py::arg("x"), py::arg("w"), py::arg("H"), py::arg("NL"), py::arg("mode"), py::arg("cell") = 0,
+        py::arg("round_bf16") = false);
   m.def("lstm_small_supported", [](int64_t H, int64_t I, int64_t NL) {
     return pdrnn_lstm_small_supported((int)H, (int)I, (int)NL) != 0;
   });

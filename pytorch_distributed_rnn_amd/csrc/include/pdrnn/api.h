@@ -178,8 +178,12 @@ int pdrnn_lstm_sw_ok(int H, int I, int NL, int cell);
 int pdrnn_lstm_sw_fits(int NL, int B, int T);
 // sequences per wave (and per workgroup) of a sequence-in-wave mode
 int pdrnn_lstm_sw_nb(int mode);
-// mode for a batch of B sequences (PDRNN_TUNE sw_mode / sw_bwd_mode override)
+// mode for a batch of B sequences (PDRNN_TUNE sw_mode / sw_bwd_mode override).
+// Forward mode 8 (layer 1's input projection on the matrix cores per 16-step
+// chunk) serves only the T that pdrnn_lstm_sw_fwd8_ok accepts: the caller
+// takes mode 6 otherwise.
 int pdrnn_lstm_sw_mode(int NL, int B, int backward);
+int pdrnn_lstm_sw_fwd8_ok(int NL, int T);
 hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t stream);
 hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t stream);
 

@@ -76,7 +76,7 @@ PDRNN_DEVICE int pick(const int (&v)[NB], int n) {
   else if constexpr (NB == 2) return n == 0 ? v[0] : v[1];
   else return n == 0 ? v[0] : n == 1 ? v[1] : v[2];
 }
-// sequences per wave of a mode: 1 (0, 2, 4, 5, 6), 2 (1, 3).  (Three per
+// sequences per wave of a mode: 1 (0, 2, 4, 5, 6, 8), 2 (1, 3).  (Three per
 // layer wave -- the mode-2 map at 960 waves for B = 1440, one per SIMD --
 // measured slower in both passes: forward +28 us, BPTT +20 us against modes
 // 6 / 3, profiles/r6/m7_ab.md; removed.)
@@ -184,9 +184,7 @@ PDRNN_DEVICE float from_odd(float v) {
 // `gk` = {2, -1} on even lanes: tanh(g) = 2 sigma(2g) - 1, {1, 0} on odd) and
 // the unit's new c, h on both lanes: c = f c + i g is the sum of one product
 // per lane (odd: f c, even: i g), h = o tanh(c) with o read from the odd lane.
-PDRNN_DEVICE Cell fwd_cell(const float (&p)[4], pdrnn_f2 gk, float c, bool odd) {
-  const float z0 = p[0] + dpp_swap1(p[1]);
-  const float z1 = p[2] + dpp_swap1(p[3]);
+PDRNN_DEVICE Cell fwd_cell_z(float z0, float z1, pdrnn_f2 gk, float c, bool odd) {
   Cell r;
   r.a0 = sig2(z0);
   r.a1 = fmaf(sig2(z1), gk.x, gk.y);
@@ -195,13 +193,14 @@ PDRNN_DEVICE Cell fwd_cell(const float (&p)[4], pdrnn_f2 gk, float c, bool odd) 
   r.h = from_odd(r.a1) * tanh_c(r.c);
   return r;
 }
+PDRNN_DEVICE Cell fwd_cell(const float (&p)[4], pdrnn_f2 gk, float c, bool odd) {
+  return fwd_cell_z(p[0] + dpp_swap1(p[1]), p[2] + dpp_swap1(p[3]), gk, c, odd);
+}
 // GRU: lane s = 0 holds r and n_x, s = 1 z and n_h (2 kA-scaled); one DPP
 // swap each gives both lanes all four, then n = tanh(n_x + r n_h) and
 // h = n + z (h_prev - n) on both.  Saved slots: a0 = r | z, a1 = n_x | n_h
 // (unscaled; the BPTT reads n_h), c = n.
-PDRNN_DEVICE Cell fwd_cell_gru(const float (&p)[4], float hprev, bool odd) {
-  const float z0 = p[0] + dpp_swap1(p[1]);
-  const float z1 = p[2] + dpp_swap1(p[3]);
+PDRNN_DEVICE Cell fwd_cell_gru_z(float z0, float z1, float hprev, bool odd) {
   Cell r;
   r.a0 = sig2(z0);
   const float a0p = dpp_swap1(r.a0), z1p = dpp_swap1(z1);
@@ -211,6 +210,9 @@ PDRNN_DEVICE Cell fwd_cell_gru(const float (&p)[4], float hprev, bool odd) {
   r.c = fmaf(sig2(fmaf(rg, nh, nx)), 2.f, -1.f);
   r.h = fmaf(zg, hprev - r.c, r.c);
   return r;
+}
+PDRNN_DEVICE Cell fwd_cell_gru(const float (&p)[4], float hprev, bool odd) {
+  return fwd_cell_gru_z(p[0] + dpp_swap1(p[1]), p[2] + dpp_swap1(p[3]), hprev, odd);
 }
 template <int CELL>
 PDRNN_DEVICE Cell fwd_cell_any(const float (&p)[4], pdrnn_f2 gk, float c, float hprev, bool odd) {
@@ -809,6 +811,240 @@ template <int CELL, bool PH = false>
 __global__ void __launch_bounds__(256) lstm_sw_fwd4_kernel(PdrnnLstmSmallFwdArgs a) { fwd4_body<CELL, PH>(a); }
 
 // ---------------------------------------------------------------------------
+// Forward, layer 1's input projection hoisted onto the matrix cores (mode 8,
+// two-layer stacks in the throughput regime, T % 16 == 0).  Mode 6's waves
+// (wave l = layer l of one sequence, <= 168 VGPRs: three waves per SIMD), and
+// BIT FOR BIT mode 6's results: every gate pre-activation is the same sum of
+// the same fp32 operations, only computed elsewhere.
+//  * Mode 6 forms a gate of layer 1 as (in.x + in.y) + (rec.x + rec.y): `in`
+//    the v_pk_fma_f32 chain over the input h^0_t (.x the even columns in
+//    ascending order, .y the odd ones; seeded with the bias for i, g) and
+//    `rec` the same over the own h_{t-1} (seeded with the bias for f, o).
+//  * W_ih^1 h^0_t does not depend on layer 1's recurrence, so the layer-1
+//    wave forms `in` for 16 steps at once with v_mfma_f32_16x16x4_f32 (M = 16
+//    time steps, N = 16 gate columns per tile, 8 tiles).  An fp32 MFMA is a
+//    k-ordered fma chain on its C operand, so one chain of 4 K steps over the
+//    even columns (k = 8 j + 2 kk; C = the bias or 0) reproduces in.x and one
+//    over the odd columns in.y: 64 MFMAs per chunk, the W_ih fragments
+//    resident in 64 VGPRs.  P[16][128] = in.x + in.y goes to an LDS tile.
+//  * The recurrent chains are split between the two lanes of a unit by gate,
+//    not by K half: lane s runs the full 32-column chains of its own two
+//    gates (s = 0: i, g from zero; s = 1: f, o from the bias) -- 8 operand
+//    reads, all lanes at one address, and 32 v_pk_fma_f32 per step instead
+//    of 64, no K-split DPP adds -- and adds its two P values (one ds_read_b64:
+//    P column 4u + 2s + j is gate row (s + 2j) H + u; row stride kPS = 132
+//    keeps the C tile's rows 4g + r on disjoint banks).
+//  * Layer 0 runs mode 6's step unchanged (its x columns share a chain with
+//    h[0, 12), so they cannot leave it without changing the sum) and also
+//    writes h^0_t into a ring of 2 chunks x 16 rows; the layer-1 wave runs one
+//    chunk behind and reads a chunk of h^0 as its A fragments: one workgroup
+//    barrier per chunk (T / 16 + 1 slots), none per step.
+// ---------------------------------------------------------------------------
+constexpr int kCT = 16;          // steps per chunk (MFMA M)
+constexpr int kPS = 4 * kH + 4;  // P row stride, floats
+// LDS floats of a workgroup: P[kCT][kPS] | h^0 ring [2][kCT][kHB] | h slots
+// [2 layers][2 parities][kHB] | layer 1's MFMA C seeds [4H] | x rows [T][kXS]
+constexpr int kF8Ring = kCT * kPS, kF8Slot = kF8Ring + 2 * kCT * kHB, kF8Bias = kF8Slot + 2 * 2 * kHB;
+constexpr int kF8X = kF8Bias + 4 * kH;
+
+template <int CELL>
+PDRNN_DEVICE float gate_scale(int q) { return kA * ((CELL == 0 ? q == 2 : q >= 2) ? 2.f : 1.f); }
+// gate row of P column p (see above)
+PDRNN_DEVICE int p_row(int p) { return (((p >> 1) & 1) + 2 * (p & 1)) * kH + (p >> 2); }
+
+template <int CELL>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3)))
+lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x;
+  const uint64_t sr_in = (a.stamps && tid == 0) ? stamp_real() : 0;  // (entry: the prologue's cost)
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // = layer
+  const int u = lane >> 1, s = lane & 1;
+  const bool odd = s != 0;
+  const int mi = lane & 15, kk = lane >> 4;  // MFMA fragment row / K index
+  const int B = a.B, T = a.T, I = a.I;
+  const int b = blockIdx.x;  // one sequence per workgroup
+  const int bsrc = a.idx ? (int)a.idx[b] : b;
+  const int nch = T / kCT;
+  float* P = smem;
+  float* ring = smem + kF8Ring;
+  float* hs = smem + kF8Slot + wv * 2 * kHB;
+  float* cseed = smem + kF8Bias;
+  float* xs = smem + kF8X;
+
+  // ---- prologue: h_{-1} = 0 (ring, slots and their pad chunks), layer 1's C
+  // seeds (the bias of i, g; 0 for f, o) in P's column order, x staged as in
+  // lstm_sw_fwd_kernel (one sequence: element loads)
+  for (int e = tid; e < kF8Bias - kF8Ring; e += 128) ring[e] = 0.f;
+  {
+    const int r = p_row(tid);
+    const float bsum = ((a.b_ih[1] ? wround(a.b_ih[1][r], a.w_bf16) : 0.f) +
+                        (a.b_hh[1] ? wround(a.b_hh[1][r], a.w_bf16) : 0.f)) * gate_scale<CELL>(r / kH);
+    cseed[tid] = (tid >> 1) & 1 ? 0.f : bsum;
+  }
+  {
+    const int tot = T * kXS, xg_ld = a.xg_ld;
+    for (int e0 = tid; e0 < tot; e0 += 4 * 128) {
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int e = min(e0 + r * 128, tot - 1);
+        const int t = e / kXS, k = e - t * kXS;
+        const float x = ldx(a.x, (int64_t)bsrc * a.x_sb + (int64_t)t * a.x_st + min(k, I - 1), a.x_bf16);
+        v[r] = k < I ? x : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int e = e0 + r * 128;
+        if (e < tot) {
+          const int t = e / kXS, k = e - t * kXS;
+          xs[e] = v[r];
+          if (a.xg_out && k < xg_ld) a.xg_out[((int64_t)b * T + t) * xg_ld + k] = v[r];
+        }
+      }
+    }
+  }
+  lds_barrier();
+
+  const __amdgpu_buffer_rsrc_t r_act = uniform_rsrc(a.act);
+  const __amdgpu_buffer_rsrc_t r_h = uniform_rsrc(a.hseq);
+  const uint32_t vo_a0 = (s * kH + u) * 4, vo_a1 = ((2 + s) * kH + u) * 4, vo_c = (4 * kH + u) * 4, vo_h = u * 4;
+  const pdrnn_f2 gk = odd ? pdrnn_f2{1.f, 0.f} : pdrnn_f2{2.f, -1.f};
+
+  uint64_t st0 = 0, sr0 = 0;
+  if (a.stamps && tid == 0) { st0 = stamp_cycles(); sr0 = stamp_real(); }
+
+  float cst = 0.f, hst = 0.f;
+  // h_t to the own parity slot, the saved rows to act / hseq
+  auto commit = [&](int t, const Cell& r) {
+    cst = r.c;
+    hst = r.h;
+    hs[(t & 1) * kHB + u] = r.h;
+    const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((wv * B + b) * T + t));
+    bstore(r.a0, r_act, vo_a0, rw * (5 * kH * 4));
+    bstore(r.a1, r_act, vo_a1, rw * (5 * kH * 4));
+    bstore(r.c, r_act, vo_c, rw * (5 * kH * 4));
+    bstore(r.h, r_h, vo_h, rw * (kH * 4));
+  };
+
+  if (wv == 0) {
+    const FwdW<6> W0 = load_fwd_w<6, CELL>(a, 0, u, s);
+    for (int c = 0; c <= nch; ++c) {
+      if (c < nch) {
+#pragma unroll 2
+        for (int i = 0; i < kCT; ++i) {
+          const int t = c * kCT + i;
+          const float* hp = hs + ((t - 1) & 1) * kHB;
+          const float* pa = odd ? hp + 12 : xs + t * kXS;
+          const float* pb = odd ? hp + 24 : hp;
+          float4 v[6];
+#pragma unroll
+          for (int cc = 0; cc < 3; ++cc) v[cc] = ld4(pa + 4 * cc);
+#pragma unroll
+          for (int cc = 0; cc < 3; ++cc) v[3 + cc] = ld4(pb + 4 * cc);
+          float p[4];
+          fwd_dot<6>(W0, v, p);
+          const Cell r = fwd_cell_any<CELL>(p, gk, cst, hst, odd);
+          commit(t, r);
+          ring[((c & 1) * kCT + i) * kHB + u] = r.h;
+        }
+      }
+      lds_barrier();
+    }
+  } else {
+    // the own two gates' rows of W_hh over all 32 columns, k pairs; bias seeds (odd lanes)
+    pdrnn_f2 wr[2][16];
+    float seed[2];
+    // B fragments of W_ih^1: column tile nt, chain e (even / odd columns), K step j -> column 8 j + 2 kk + e
+    float bw[8][2][4];
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int q = s + 2 * jj, r = q * kH + u;
+      const float sc = gate_scale<CELL>(q);
+#pragma unroll
+      for (int cc = 0; cc < 8; ++cc) {
+        const float* w = a.w_hh[1] + (int64_t)r * kH + 4 * cc;
+        wr[jj][2 * cc] = pdrnn_f2{wround(w[0], a.w_bf16) * sc, wround(w[1], a.w_bf16) * sc};
+        wr[jj][2 * cc + 1] = pdrnn_f2{wround(w[2], a.w_bf16) * sc, wround(w[3], a.w_bf16) * sc};
+      }
+      const float bsum = ((a.b_ih[1] ? wround(a.b_ih[1][r], a.w_bf16) : 0.f) +
+                          (a.b_hh[1] ? wround(a.b_hh[1][r], a.w_bf16) : 0.f)) * sc;
+      seed[jj] = odd ? bsum : 0.f;
+    }
+#pragma unroll
+    for (int nt = 0; nt < 8; ++nt) {
+      const int r = p_row(16 * nt + mi);
+      const float sc = gate_scale<CELL>(r / kH);
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          bw[nt][e][j] = wround(a.w_ih[1][(int64_t)r * kH + 8 * j + 2 * kk + e], a.w_bf16) * sc;
+    }
+    for (int c = 0; c <= nch; ++c) {
+      if (c > 0) {
+        // ---- chunk c - 1: P = in.x + in.y for its 16 steps
+        {
+          const float* hr = ring + (((c - 1) & 1) * kCT + mi) * kHB + 2 * kk;
+          pdrnn_f2 av[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) av[j] = *reinterpret_cast<const pdrnn_f2*>(hr + 8 * j);
+#pragma unroll
+          for (int nt = 0; nt < 8; ++nt) {
+            const float b0 = cseed[16 * nt + mi];
+            f32x4 ce = {b0, b0, b0, b0}, co = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              ce = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].x, bw[nt][0][j], ce, 0, 0, 0);
+              co = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].y, bw[nt][1][j], co, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) P[(4 * kk + r) * kPS + 16 * nt + mi] = ce[r] + co[r];
+          }
+        }
+#pragma unroll 2
+        for (int i = 0; i < kCT; ++i) {
+          const int t = (c - 1) * kCT + i;
+          const float* hp = hs + ((t - 1) & 1) * kHB;
+          float4 v[8];
+#pragma unroll
+          for (int cc = 0; cc < 8; ++cc) v[cc] = ld4(hp + 4 * cc);
+          const pdrnn_f2 pin = *reinterpret_cast<const pdrnn_f2*>(P + i * kPS + 2 * lane);
+          pdrnn_f2 acc[2] = {{seed[0], 0.f}, {seed[1], 0.f}};
+#pragma unroll
+          for (int cc = 0; cc < 8; ++cc)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+              acc[jj] = pfma(wr[jj][2 * cc], lo2(v[cc]), acc[jj]);
+              acc[jj] = pfma(wr[jj][2 * cc + 1], hi2(v[cc]), acc[jj]);
+            }
+          const float z0 = (acc[0].x + acc[0].y) + pin.x, z1 = (acc[1].x + acc[1].y) + pin.y;
+          Cell r;
+          if constexpr (CELL == 0) r = fwd_cell_z(z0, z1, gk, cst, odd);
+          else r = fwd_cell_gru_z(z0, z1, hst, odd);
+          commit(t, r);
+        }
+      }
+      lds_barrier();
+    }
+  }
+  if (a.stamps && tid == 0) {
+    uint64_t* st = a.stamps + (uint64_t)blockIdx.x * 8;
+    st[0] = st0; st[1] = stamp_cycles(); st[2] = sr0; st[3] = stamp_real();
+  }
+
+  // ---- epilogue: h_n / c_n, then the fused head on the top layer's h_T ----
+  if (!odd && a.hn) a.hn[((int64_t)wv * B + b) * kH + u] = hst;
+  if (!odd && a.cn) a.cn[((int64_t)wv * B + b) * kH + u] = cst;
+  if (a.head_w && wv == 1) motion_head(a, b, hst, u, odd);
+  if (a.stamps && tid == 0) {
+    uint64_t* st = a.stamps + (uint64_t)blockIdx.x * 8;
+    st[4] = sr_in; st[5] = stamp_real(); st[6] = stamp_cu();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Backward (lean contract: zero initial state, dL/dh_T of the top layer only,
 // weight gradients deferred to pdrnn_lstm_small_dw)
 // ---------------------------------------------------------------------------
@@ -1370,6 +1606,16 @@ hipError_t launch_fwd(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
     hipLaunchKernelGGL((lstm_sw_fwd_kernel<NL, MODE, 0>), dim3(grid), dim3(block), fwd_lds(NL, NB, a->T), st, *a);
   return hipGetLastError();
 }
+// Mode 8: 14,144 bytes of LDS plus the staged x rows (48 T).  Six workgroups
+// (three waves per SIMD) share a CU's 160 KiB only up to 26,624 bytes each
+// (2 KiB granules): T <= 256; longer sequences take mode 6.
+size_t fwd8_lds(int T) { return sizeof(float) * ((size_t)kF8X + (size_t)T * kXS); }
+hipError_t launch_fwd8(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
+  if (!pdrnn_lstm_sw_fwd8_ok(a->NL, a->T)) return hipErrorInvalidValue;  // (the planner falls back to mode 6)
+  if (a->cell == 1) hipLaunchKernelGGL(lstm_sw_fwd8_kernel<1>, dim3(a->B), dim3(128), fwd8_lds(a->T), st, *a);
+  else hipLaunchKernelGGL(lstm_sw_fwd8_kernel<0>, dim3(a->B), dim3(128), fwd8_lds(a->T), st, *a);
+  return hipGetLastError();
+}
 hipError_t launch_fwd4(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
   const size_t lds = sizeof(float) * (2 * 2 * kHB + (size_t)a->T * kXS);
   if (a->phase_stamps && a->stamps && a->cell == 0)
@@ -1394,6 +1640,10 @@ hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, hipStream_t st) {
 
 using namespace pdrnn;
 
+extern "C" int pdrnn_lstm_sw_fwd8_ok(int NL, int T) {
+  return (NL == 2 && T > 0 && T % kCT == 0 && 6 * ((fwd8_lds(T) + 2047) / 2048 * 2048) <= 160 * 1024) ? 1 : 0;
+}
+
 
 extern "C" int pdrnn_lstm_sw_ok(int H, int I, int NL, int cell) {
   return (H == kH && I >= 1 && I <= kXS && (NL == 1 || NL == 2) && (cell == 0 || cell == 1)) ? 1 : 0;
@@ -1414,8 +1664,11 @@ extern "C" int pdrnn_lstm_sw_fits(int NL, int B, int T) {
 // wave per layer up to one wave per SIMD (mode 2) -- the forward two waves
 // per layer up to half a wave per SIMD (mode 5: 56.5 vs 62.0 us at B = 180,
 // 73.1 vs 81.8 at 512, slower above, profiles/r5/sw/fwd4_probe.log); above, the forward keeps
-// that map at three waves per SIMD (mode 6) and the backward takes two
-// sequences per wave (mode 3).  Up to two workgroups per CU the backward
+// that map at three waves per SIMD with layer 1's input projection hoisted
+// onto the matrix cores per 16-step chunk (mode 8: the same bits as mode 6,
+// the per-step map, and 1.0-1.5 % on the headline step at B = 1440 / 1152,
+// profiles/r7/fwd_chunked.md; mode 6 where pdrnn_lstm_sw_fwd8_ok refuses T)
+// and the backward takes two sequences per wave (mode 3).  Up to two workgroups per CU the backward
 // forms the weight gradients itself (mode 4: two more waves per workgroup on
 // the matrix cores, no dW launch; 55.7 us against 54.7 + 16.9 at B = 180,
 // profiles/r5/sw/dw4_probe.log; T % 4 == 0, the caller falls back to mode 2
@@ -1426,14 +1679,14 @@ extern "C" int pdrnn_lstm_sw_mode(int NL, int B, int backward) {
   int m = pdrnn_tune_int(backward ? "sw_bwd_mode" : "sw_mode", -1);
   if (m < 0 && backward) m = pdrnn_tune_int("sw_mode", -1);
   if (m >= 0) {
-    if (m >= 0 && m <= 6 && (m < 2 || NL == 2) && (m != 6 || !backward) && (m != 4 || backward) &&
-        (m != 5 || !backward))
+    if (((m >= 0 && m <= 6) || m == 8) && (m < 2 || NL == 2) && (m != 6 || !backward) && (m != 4 || backward) &&
+        (m != 5 || !backward) && (m != 8 || !backward))
       return m;
   }
   const int simds = 4 * sw_cus();
   // (modes 4 / 5: four waves per workgroup, two workgroups per CU)
   if (NL == 2 && 2 * B <= simds) return backward ? 4 : 5;
-  if (NL == 2) return B <= simds ? 2 : backward ? 3 : 6;
+  if (NL == 2) return B <= simds ? 2 : backward ? 3 : 8;  // (8: the caller falls back to 6 for the T it does not serve)
   return B <= simds ? 0 : 1;
 }
 
@@ -1474,6 +1727,7 @@ extern "C" hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode
   if (!pdrnn_lstm_sw_fits(a->NL, a->B, a->T)) return hipErrorInvalidValue;  // 2 GiB descriptor range
   if (a->head_w && (a->C > 16 || a->C < 1 || !a->labels || !a->slab || !a->dh_top)) return hipErrorInvalidValue;
   if (a->xg_out && (a->xg_ld < a->I || a->xg_ld > kXS)) return hipErrorInvalidValue;
+  if (mode == 8) return launch_fwd8(a, st);
   if (fwd_lds(a->NL, mode_nb(mode), a->T) > 64 * 1024) return hipErrorInvalidConfiguration;
   if (a->NL == 1) {
     if (mode == 0) return launch_fwd<1, 0>(a, st);
