@@ -1236,8 +1236,24 @@ std::vector<Tensor> lstm_large_fwd(const Tensor& xp, const std::vector<Tensor>& 
   return {hseq, cseq, acts};
 }
 
+// How the per-step backward runs a shape: K-slices of the step GEMM (1 = no
+// split), their tile (big: 128x128 instead of 32x32), and whether the
+// unsplit step is the ping-pong GEMM + cell pair instead of the fused kernel.
+// lstm_large_bwd fills its launch arguments from this; lstm_large_bwd_plan
+// returns it to the tests, which pin every case to the kernel it names.
+struct LargeBwdPlan {
+  int splitk, big, pp;
+};
+LargeBwdPlan large_bwd_plan(int B, int H, int ndir, int dt) {
+  LargeBwdPlan p{1, 0, 0};
+  p.splitk = pdrnn_lstm_large_bwd_splitk(B, H, ndir, &p.big);
+  // large batch: ping-pong GEMM + cell kernel (fp32 dh through ws)
+  p.pp = p.splitk == 1 ? pdrnn_lstm_large_bwd_pp(B, H, ndir, dt) : 0;
+  return p;
+}
+
 // Backward of one layer: returns dgates [ndir, T, B, 4H] (16-bit), dh0, dc0
-// [ndir, B, H] f32.  wt: ndir x [H, 4H] (transposed gate-interleaved W_hh).
+// [ndir, B, H] f32.  wt: ndir x [H, 4H] (W_hh^T, gate-blocked columns).
 std::vector<Tensor> lstm_large_bwd(const optional<Tensor>& dout, const optional<Tensor>& dhn,
                                    const optional<Tensor>& dcn, const std::vector<Tensor>& wt, const Tensor& cseq,
                                    const Tensor& acts, const optional<Tensor>& c0, int64_t H, int64_t reverse_mask,
@@ -1288,11 +1304,10 @@ std::vector<Tensor> lstm_large_bwd(const optional<Tensor>& dout, const optional<
     dd.dh0 = dh0.data_ptr<float>() + d * B * H;
     dd.dc0 = dc0.data_ptr<float>() + d * B * H;
   }
-  int big = 0;
-  a.splitk = pdrnn_lstm_large_bwd_splitk((int)B, (int)H, ndir, &big);
-  a.splitk_big = big;
-  // large batch: ping-pong GEMM + cell kernel (fp32 dh through ws)
-  a.bwd_pp = a.splitk == 1 ? pdrnn_lstm_large_bwd_pp((int)B, (int)H, ndir, dt) : 0;
+  const LargeBwdPlan plan = large_bwd_plan((int)B, (int)H, ndir, dt);
+  a.splitk = plan.splitk;
+  a.splitk_big = plan.big;
+  a.bwd_pp = plan.pp;
   Tensor ws;
   if (a.splitk > 1 || a.bwd_pp) {
     ws = at::empty({a.splitk, 2, B, H}, o32);
@@ -1801,6 +1816,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return large_persist_plan((int)B, (int)H, (int)ndir, true, (int)dtype, tile) != 0;
         },
         "1 when lstm_large_bwd's recurrence would take the grid-synced persistent path");
+  m.def("lstm_large_bwd_plan",
+        [](int64_t B, int64_t H, int64_t ndir, int64_t dtype) {
+          // read-only: launches nothing (dtype 0 bf16, 1 fp16, 2 fp32)
+          const LargeBwdPlan p = large_bwd_plan((int)B, (int)H, (int)ndir, (int)dtype);
+          return std::make_tuple(p.splitk, p.big, p.pp);
+        },
+        "(splitk, big, pp) of lstm_large_bwd's per-step kernels at this shape: K-slices of the step GEMM, "
+        "128x128 slices instead of 32x32, ping-pong GEMM + cell pair");
   m.def("lstm_large_bwd", &lstm_large_bwd, "large-H LSTM layer BPTT (MFMA step kernels) -> dgates, dh0, dc0");
   m.def("lstm_large_supported", [](int64_t H) { return pdrnn_lstm_large_supported((int)H) != 0; });
   m.def("lstm_rows_range_supported", [](int64_t H) { return rows_f32_on() && pdrnn_lstm_rows_f32_supported((int)H, 2) != 0; });

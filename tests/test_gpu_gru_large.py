@@ -4,6 +4,7 @@ csrc/kernels/lstm_large.hip) vs the fp32 torch.nn.GRU on the same
 import pytest
 import torch
 
+from pytorch_distributed_rnn_amd import _ext
 from pytorch_distributed_rnn_amd.models.rnn import GRU
 from pytorch_distributed_rnn_amd.ops import gru_large
 
@@ -75,9 +76,14 @@ def test_large_gru_every_tile(tile, monkeypatch):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("bwd", ["0", "2"])
 def test_large_gru_pingpong_step_matches_torch(dt, bwd, monkeypatch):
-    set_tune(monkeypatch, large_pp="2")
-    monkeypatch.setenv("PDRNN_TUNE large_pp_BWD", bwd)
-    test_large_gru_matches_torch(dt, 256, 1, True, 300, 3, 64)
+    """Forward on the ping-pong step kernel; backward on the ping-pong GEMM +
+    cell pair ("2") or not ("0").  The pair only replaces the unsplit step and
+    B 300 plans 2 K-slices at this size, so its rows run at B 520."""
+    set_tune(monkeypatch, large_pp="2", large_pp_bwd=bwd)
+    B = 520 if bwd == "2" else 300
+    splitk, _, pair = _ext.require().lstm_large_bwd_plan(B, 256, 2, 0 if dt == torch.bfloat16 else 1)
+    assert (splitk, pair) == (1, 1) if bwd == "2" else pair == 0
+    test_large_gru_matches_torch(dt, 256, 1, True, B, 3, 64)
 
 
 def test_large_gru_no_bias_no_state():

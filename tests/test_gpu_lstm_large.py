@@ -88,16 +88,24 @@ def test_large_lstm_matches_torch(dt, H, L, bi, B, T, I):
         assert _rel(p.grad, q.grad) < 4e-2, n
 
 
-@pytest.mark.parametrize("mode", ["gemmpipe", "gemm+cell"])
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("H,L,bi,B,T,I", [(256, 1, True, 300, 3, 64), (512, 2, False, 520, 4, 128)])
+# (256, bidirectional, B 300) plans 2 K-slices in the backward, and the GEMM +
+# cell pair only replaces the unsplit step: its pair rows run at B 520
+_PP_SHAPES = {"gemmpipe": [(256, 1, True, 300, 3, 64), (512, 2, False, 520, 4, 128)],
+              "gemm+cell": [(256, 1, True, 520, 3, 64), (512, 2, False, 520, 4, 128)]}
+
+
+@pytest.mark.parametrize("dt,H,L,bi,B,T,I,mode", [
+    pytest.param(dt, *shape, mode, id="-".join(map(str, shape)) + f"-dt{k}-{mode}")
+    for mode in ("gemmpipe", "gemm+cell") for k, dt in enumerate([torch.bfloat16, torch.float16])
+    for shape in _PP_SHAPES[mode]])
 def test_large_lstm_pingpong_step_matches_torch(dt, H, L, bi, B, T, I, mode, monkeypatch):
     """The 256x256 ping-pong step kernels, forced at shapes below their
     occupancy threshold (batch not a multiple of 256): forward with the
     two-pass cell epilogue, backward either on the fused GemmPipe step kernel
     or as the ping-pong GEMM into the dh workspace + the cell kernel."""
-    set_tune(monkeypatch, large_pp="2")
-    monkeypatch.setenv("PDRNN_TUNE large_pp_BWD", "2" if mode == "gemm+cell" else "0")
+    set_tune(monkeypatch, large_pp="2", large_pp_bwd="2" if mode == "gemm+cell" else "0")
+    splitk, _, pair = _ext.require().lstm_large_bwd_plan(B, H, 2 if bi else 1, 0 if dt == torch.bfloat16 else 1)
+    assert (splitk, pair) == (1, 1) if mode == "gemm+cell" else pair == 0
     test_large_lstm_matches_torch(dt, H, L, bi, B, T, I)
 
 
