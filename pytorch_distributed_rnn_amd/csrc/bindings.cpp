@@ -272,11 +272,21 @@ void set_offsets(Args& a, const StackLayout& L, int64_t NL) {
   a.P = L.P;
 }
 
+// A stack's parameter list as Python passes it: None (a layer's absent bias)
+// becomes an undefined tensor.
+std::vector<Tensor> stack_tensors(const std::vector<optional<Tensor>>& w) {
+  std::vector<Tensor> out;
+  out.reserve(w.size());
+  for (const auto& t : w) out.push_back(t.has_value() ? *t : Tensor());
+  return out;
+}
+
 // Returns {out_or_hseq, hn, cn, act}.
-std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx, const std::vector<Tensor>& w,
-                                   const optional<Tensor>& h0, const optional<Tensor>& c0, int64_t H, int64_t NL,
-                                   bool batch_first, bool save, bool need_out, int64_t nb, int64_t split,
-                                   int64_t cell) {
+std::vector<Tensor> lstm_small_fwd(const Tensor& x, const optional<Tensor>& idx,
+                                   const std::vector<optional<Tensor>>& w_in, const optional<Tensor>& h0,
+                                   const optional<Tensor>& c0, int64_t H, int64_t NL, bool batch_first, bool save,
+                                   bool need_out, int64_t nb, int64_t split, int64_t cell) {
+  const std::vector<Tensor> w = stack_tensors(w_in);
   CHECK_HIP_TENSOR(x);
   TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "x must be float32 or bfloat16");
   TORCH_CHECK(x.dim() == 3, "x must be 3-D");
@@ -356,12 +366,14 @@ std::vector<Tensor> lstm_sw_fwd(const Tensor& x, const std::vector<Tensor>& w, i
 }
 
 // Returns {dparams_flat[P] (nn.LSTM parameter order), dx, dh0, dc0}.
-std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx, const std::vector<Tensor>& w,
-                                   const optional<Tensor>& h0, const optional<Tensor>& c0, const Tensor& hseq,
-                                   const Tensor& act, const optional<Tensor>& dout, const optional<Tensor>& dhn,
+std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx,
+                                   const std::vector<optional<Tensor>>& w_in, const optional<Tensor>& h0,
+                                   const optional<Tensor>& c0, const Tensor& hseq, const Tensor& act,
+                                   const optional<Tensor>& dout, const optional<Tensor>& dhn,
                                    const optional<Tensor>& dcn, int64_t H, int64_t NL, bool batch_first,
                                    bool need_dx, bool need_dh0, int64_t nb, int64_t split,
                                    const optional<Tensor>& grad_accum, int64_t cell) {
+  const std::vector<Tensor> w = stack_tensors(w_in);
   CHECK_HIP_TENSOR(x);
   const c10::DeviceGuard guard(x.device());
   const int64_t I = x.size(2);
@@ -1714,6 +1726,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_small_max_split", [](int64_t H, int64_t NL, bool backward) {
     return pdrnn_lstm_small_max_split((int)H, (int)NL, backward ? 1 : 0);
   });
+  m.def("lstm_small_bwd_grid", [](int64_t H, int64_t NL, int64_t T, int64_t B, int64_t nb, int64_t split) {
+    return pdrnn_lstm_small_bwd_grid((int)H, (int)NL, (int)T, (int)B, (int)nb, (int)split);
+  }, "workgroups (= slab rows) of lstm_small_bwd for this shape: below the batch tiles, the grid is persistent");
   m.def("lstm_small_step_one_launch", [](int64_t H, int64_t NL, int64_t T, int64_t B, int64_t nb_fwd,
                                          int64_t split_fwd, int64_t nb_bwd, int64_t split_bwd) {
     const HeadStepPlan p = plan_small_family(H, NL, T, B, nb_fwd, split_fwd, nb_bwd, split_bwd);

@@ -359,10 +359,13 @@ lstm_small_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
           *w3 = s == 0 ? cn : h;
           continue;
         }
-        const float ig = sigmoidf_fast(acc[0]);
-        const float fg = sigmoidf_fast(acc[1]);
-        const float gg = tanhf_fast(acc[2]);
-        const float og = sigmoidf_fast(acc[3]);
+        // (two sequences per workgroup, inference) the rows are pre-scaled
+        // here too: acc = -log2(e) z, doubled for the g gate
+        static_assert(S == 2, "the activations below expect the pre-scaled rows of the 2-lane map");
+        const float ig = fast_rcp(1.f + __builtin_amdgcn_exp2f(acc[0]));
+        const float fg = fast_rcp(1.f + __builtin_amdgcn_exp2f(acc[1]));
+        const float gg = fmaf(fast_rcp(1.f + __builtin_amdgcn_exp2f(acc[2])), 2.f, -1.f);
+        const float og = fast_rcp(1.f + __builtin_amdgcn_exp2f(acc[3]));
         const float cn = fmaf(fg, c[n], ig * gg);
         const float h = og * tanhf_fast(cn);
         c[n] = cn;
