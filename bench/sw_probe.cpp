@@ -3,13 +3,15 @@
 // K-split kernels of lstm_small.hip on the same buffers.  No torch: builds in
 // seconds and runs on a fresh GPU box without the torch import.
 //
-//   bench/sw_probe.sh            (build + run: B=180 and 1440, every mode)
-//   sw_probe B [reps] [modes...]  mode 0-3, 6, 8 = sequence-in-wave (lstm_sw.hip; 6 and 8 are
-//                                 forward maps, their backward runs map 3), 4 = forward 2 +
-//                                 register-dW backward 4, 54 = forward 5 + backward 4,
+//   bench/sw_probe.sh            (build + run: B=180 and 1440, every map pair)
+//   sw_probe B [reps] [modes...]  F/B = sequence-in-wave forward map F, backward map B (the wave
+//                                 map table of lstm_sw.hip: two-layer forwards 2, 5, 6, 8,
+//                                 backwards 2, 3, 4); the pair is resolved by pdrnn_lstm_sw_plan
+//                                 as PDRNN_TUNE sw_mode=F,sw_bwd_mode=B, so what the table does
+//                                 not list keeps the plan's default, as does a B left out;
 //                                 9 = lstm_small (gate-split / K-split family)
-//   (mode 7, the bf16 matrix-core recurrence lstm_mb.hip, was removed in round 6:
-//   1.2-3.3x slower than these fp32 VALU kernels, docs/DESIGN.md §2b)
+//   (the bf16 matrix-core recurrence lstm_mb.hip was removed in round 6: 1.2-3.3x slower than
+//   these fp32 VALU kernels, docs/DESIGN.md §2b)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -147,9 +149,9 @@ static double maxrel(const std::vector<float>& got, const std::vector<double>& r
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 1440;
   const int reps = argc > 2 ? atoi(argv[2]) : 20;
-  std::vector<int> modes;
-  for (int i = 3; i < argc; ++i) modes.push_back(atoi(argv[i]));
-  if (modes.empty()) modes = {2, 3, 6, 9};
+  std::vector<std::string> modes;
+  for (int i = 3; i < argc; ++i) modes.push_back(argv[i]);
+  if (modes.empty()) modes = {"2/2", "2/3", "2/4", "5/4", "5/2", "6/3", "8/3", "9"};
   const int T = 128, NL = 2;
   const int N = B + 37;  // dataset rows; the batch gathers a random subset
   std::mt19937 rng(1234);
@@ -179,24 +181,6 @@ int main(int argc, char** argv) {
 
   Ref R;
   reference(NL, B, T, x, idx, lab, wih, whh, bih, bhh, hw, hb, R);
-  // the bf16 model's reference: weights, biases and inputs rounded to bf16
-  // (the recurrence itself in fp64)
-  Ref Rb;
-  if (std::find(modes.begin(), modes.end(), 7) != modes.end()) {
-    auto rb = [](std::vector<float> v) {
-      for (auto& e : v) {
-        uint32_t u;
-        std::memcpy(&u, &e, 4);
-        u = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
-        std::memcpy(&e, &u, 4);
-      }
-      return v;
-    };
-    std::vector<float> wih_b[2], whh_b[2], bih_b[2], bhh_b[2];
-    for (int l = 0; l < NL; ++l) { wih_b[l] = rb(wih[l]); whh_b[l] = rb(whh[l]); bih_b[l] = rb(bih[l]); bhh_b[l] = rb(bhh[l]); }
-    reference(NL, B, T, rb(x), idx, lab, wih_b, whh_b, bih_b, bhh_b, hw, hb, Rb);
-  }
-
   auto up = [](const void* src, size_t bytes) {
     void* d = nullptr;
     CK(hipMalloc(&d, bytes));
@@ -235,7 +219,7 @@ int main(int argc, char** argv) {
   }
   const int chunks = pdrnn_lstm_small_dw_chunks(H, NL, B, T);
   float* slab;
-  CK(hipMalloc(&slab, (size_t)std::max(std::max(chunks, 1), B) * P * 4));  // (mode 4: one row per sequence)
+  CK(hipMalloc(&slab, (size_t)std::max(std::max(chunks, 1), B) * P * 4));  // (register dW: one row per sequence)
 
   PdrnnLstmSmallFwdArgs f{};
   f.x = dx; f.idx = didx; f.x_sb = (int64_t)T * I; f.x_st = I;
@@ -267,8 +251,8 @@ int main(int argc, char** argv) {
   uint64_t* stamps = nullptr;
   const bool want_stamps = getenv("SW_STAMPS") != nullptr;
   if (want_stamps) {
-    CK(hipMalloc(&stamps, (size_t)B * 8 * 8 + 4096));  // + the MB_DEBUG dump area
-    CK(hipMemset(stamps, 0, (size_t)B * 8 * 8 + 4096));
+    CK(hipMalloc(&stamps, (size_t)B * 8 * 8));
+    CK(hipMemset(stamps, 0, (size_t)B * 8 * 8));
     f.stamps = stamps;
   }
   hipStream_t st;
@@ -280,22 +264,31 @@ int main(int argc, char** argv) {
   int cus = 0;
   CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
   printf("B=%d T=%d NL=%d CUs=%d reps=%d\n", B, T, NL, cus, reps);
-  for (int mode : modes) {
-    const bool old = mode == 9;
-    const bool mb = false;
-    const bool rdw = mode == 4 || mode == 54;  // the backward forms the dW itself (no dz stores, no dW launch)
-    const Ref& RR = mb ? Rb : R;
-    const double tol = mb ? 3e-2 : 1e-4;
+  for (const std::string& mode : modes) {
+    const bool old = mode == "9";
+    // the pair goes through the planner as the overrides it is: what the
+    // table does not list for a pass falls back to the plan's own choice
+    PdrnnLstmSwPlan plan{};
+    if (!old) {
+      const size_t sl = mode.find('/');
+      std::string tune = "sw_mode=" + mode.substr(0, sl);
+      if (sl != std::string::npos) tune += ",sw_bwd_mode=" + mode.substr(sl + 1);
+      setenv("PDRNN_TUNE", tune.c_str(), 1);
+      if (!pdrnn_lstm_sw_plan(NL, B, T, &plan)) { fprintf(stderr, "B=%d T=%d: not served\n", B, T); return 2; }
+    }
+    const bool rdw = plan.register_dw != 0;  // the backward forms the dW itself (no dz stores, no dW launch)
+    const Ref& RR = R;
+    const double tol = 1e-4;
     const int nb_old_f = 1, sp_old_f = B > 1024 ? 2 : 1;
     const int nb_old_b = old ? pdrnn_lstm_small_bwd_dwout_nb(H, NL, T, B) : 1;
     const int grid_old_b = old ? pdrnn_lstm_small_bwd_dwout_grid(H, NL, T, B, nb_old_b) : 0;
     auto run_fwd = [&]() {
       if (old) CK(pdrnn_lstm_small_fwd(&f, H, nb_old_f, sp_old_f, 1, st));
-      else CK(pdrnn_lstm_sw_fwd(&f, mode == 4 ? 2 : mode == 54 ? 5 : mode, st));  // 4: backward-only map
+      else CK(pdrnn_lstm_sw_fwd(&f, plan.fwd_map, st));
     };
     auto run_bwd = [&]() {
       if (old) CK(pdrnn_lstm_small_bwd_dwout(&bk, H, grid_old_b, nb_old_b, st));
-      else CK(pdrnn_lstm_sw_bwd(&bk, (mode == 6 || mode == 8) ? 3 : mode == 54 ? 4 : mode == 5 ? 2 : mode, st));  // 54: fwd 5 + bwd 4
+      else CK(pdrnn_lstm_sw_bwd(&bk, plan.bwd_map, st));
     };
     // correctness: one forward, check; one backward, check
     CK(hipMemsetAsync(act, 0, n_act * 4, st));
@@ -309,35 +302,6 @@ int main(int argc, char** argv) {
     const double e_act = maxrel(h_act, RR.act, rows, 5 * H, 5 * H, 5 * H);
     const double e_h = maxrel(hseq_only, RR.hseq, rows, H, H, H);
     const double e_dht = maxrel(h_dht, RR.dhtop, B, H, H, H);
-    if (getenv("PROBE_DUMP") && mb && want_stamps) {  // MB_DEBUG build: the h image of step 0, tile 0
-      std::vector<uint32_t> d(256), wa(256);
-      CK(hipMemcpy(d.data(), reinterpret_cast<uint32_t*>(stamps) + 256, 1024, hipMemcpyDeviceToHost));
-      CK(hipMemcpy(wa.data(), reinterpret_cast<uint32_t*>(stamps) + 512, 1024, hipMemcpyDeviceToHost));
-      int badw = 0;
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const uint32_t wv = wa[lane * 4 + j / 2];
-          const uint32_t bits = (j & 1 ? wv >> 16 : wv & 0xFFFF) << 16;
-          float got;
-          std::memcpy(&got, &bits, 4);
-          const int ai = lane & 15, row = (ai & 3) * H + 8 * (ai >> 2) + 0, k = 8 * (lane >> 4) + j;
-          const float ref = whh[0][row * H + k];
-          if (std::fabs(got - ref) > 0.01f && badw++ < 6) printf("  W_hh frag lane %d j %d got %.4f ref %.4f\n", lane, j, got, ref);
-        }
-      printf("  W_hh A fragment (wave 0, m-tile 0): %d of 512 off\n", badw);
-      int bad = 0;
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const uint32_t wv = d[lane * 4 + j / 2];
-          const uint32_t bits = (j & 1 ? wv >> 16 : wv & 0xFFFF) << 16;
-          float got;
-          std::memcpy(&got, &bits, 4);
-          const int n = lane & 15, u = 8 * (lane >> 4) + j;
-          const double ref = RR.hseq[((size_t)n * T + 0) * H + u];
-          if (std::fabs(got - ref) > 0.02 && bad++ < 8) printf("  img n=%d u=%d got %.4f ref %.4f\n", n, u, got, ref);
-        }
-      printf("  h image step 0: %d of 512 off\n", bad);
-    }
     if (getenv("PROBE_DUMP") && e_act > tol) {  // first mismatching activations: (l, b, t, slot)
       int shown = 0;
       for (size_t r = 0; r < rows && shown < 12; ++r)
@@ -353,7 +317,7 @@ int main(int argc, char** argv) {
     run_bwd();
     CK(hipStreamSynchronize(st));
     CK(hipMemcpy(h_act.data(), act, n_act * 4, hipMemcpyDeviceToHost));
-    const double e_dz = rdw ? 0.0 : maxrel(h_act, RR.dz, rows, 5 * H, 4 * H, 4 * H);  // (4: no dz stores)
+    const double e_dz = rdw ? 0.0 : maxrel(h_act, RR.dz, rows, 5 * H, 4 * H, 4 * H);  // (register dW: no dz stores)
     // the summed weight gradients (slab rows), against the first mode's
     {
       int nrows = B;
@@ -387,9 +351,11 @@ int main(int argc, char** argv) {
     float tf = 0, tb = 0, tw = 0;
     CK(hipEventElapsedTime(&tf, e0, e1)); CK(hipEventElapsedTime(&tb, e1, e2)); CK(hipEventElapsedTime(&tw, e2, e3));
     const double uf = 1e3 * tf / reps, ub = 1e3 * tb / reps, uw = 1e3 * tw / reps;
-    printf("mode %d%s: fwd %7.1f us (%4.0f cyc/it @2.4)  bwd %7.1f us (%4.0f cyc/it)  dW %6.1f us | err act %.2e h %.2e "
+    char maps[48] = " (lstm_small)";
+    if (!old) snprintf(maps, sizeof(maps), " (fwd map %d, bwd map %d)", plan.fwd_map, plan.bwd_map);
+    printf("mode %s%s: fwd %7.1f us (%4.0f cyc/it @2.4)  bwd %7.1f us (%4.0f cyc/it)  dW %6.1f us | err act %.2e h %.2e "
            "dhT %.2e dz %.2e %s\n",
-           mode, old ? " (lstm_small)" : mb ? " (bf16 mfma)" : "", uf, uf * 2400.0 / (T + NL - 1), ub,
+           mode.c_str(), maps, uf, uf * 2400.0 / (T + NL - 1), ub,
            ub * 2400.0 / (T + NL - 1), uw, e_act, e_h, e_dht, e_dz,
            (e_act < tol && e_h < tol && e_dht < tol && e_dz < tol) ? "OK" : "MISMATCH");
     if (!rdw && getenv("PROBE_OVERLAP")) {
@@ -417,7 +383,8 @@ int main(int argc, char** argv) {
     if (want_stamps) {
       std::vector<uint64_t> hs((size_t)B * 8);
       CK(hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-      const int g = mode == 3 || mode == 1 ? (B + 1) / 2 : B;
+      const int fnb = old ? 1 : plan.fwd_nb;
+      const int g = (B + fnb - 1) / fnb;  // the forward's workgroups
       double lp[2] = {0, 0}, wt[2] = {0, 0}, lo = 0;
       for (int i = 0; i < g; ++i) {
         lo += (double)(hs[i * 8 + 1] - hs[i * 8 + 0]);

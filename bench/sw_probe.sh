@@ -3,6 +3,8 @@
 # sequence-in-wave kernel probe (bench/sw_probe.cpp).
 #   bench/sw_probe.sh build
 #   bench/sw_probe.sh run TAG [B...]
+# run: the probe's default mode list, every forward map with a backward map of
+# a two-layer stack as F/B (2/2 2/3 2/4 5/4 5/2 6/3 8/3) and 9, the gate-split family
 set -e
 cd "$(dirname "$0")/.."
 K=pytorch_distributed_rnn_amd/csrc/kernels

@@ -517,21 +517,18 @@ HeadStepPlan plan_head_step(const HeadStepShape& s) {
   const int dw_mode = pdrnn_lstm_small_dwout_ok(H, NL, T);
   p.sw = s.sw_on && pdrnn_lstm_sw_ok(H, I, NL, cell) == 1 && dw_mode != 0 && T <= 640 &&
          pdrnn_lstm_sw_fits(NL, B, T) == 1;
+  // Their wave maps come from the family's own plan (pdrnn_lstm_sw_plan).  In
+  // the latency regime it offers one launch for forward + BPTT
+  // (lstm_sw_step_kernel) and register dW: the BPTT waves form dW on the
+  // matrix cores, one slab row per sequence, no dW launch.
+  PdrnnLstmSwPlan sp{};
+  p.sw = p.sw && pdrnn_lstm_sw_plan(NL, B, T, &sp) == 1;
   if (p.sw) {
-    p.sw_fmode = pdrnn_lstm_sw_mode(NL, B, 0);
-    p.sw_bmode = pdrnn_lstm_sw_mode(NL, B, 1);
-    if (p.sw_bmode == 4 && T % 4) p.sw_bmode = 2;  // register dW: whole 4-step K steps
-    if (p.sw_fmode == 8 && !pdrnn_lstm_sw_fwd8_ok(NL, T)) p.sw_fmode = 6;  // whole 16-step chunks, six workgroups per CU
-    // sequences per workgroup: two in modes 1 / 3 (mode 5, the four-wave forward, runs one)
-    p.sw_fnb = pdrnn_lstm_sw_nb(p.sw_fmode);
-    p.sw_bnb = pdrnn_lstm_sw_nb(p.sw_bmode);
+    p.sw_fmode = sp.fwd_map; p.sw_bmode = sp.bwd_map;
+    p.sw_fnb = sp.fwd_nb; p.sw_bnb = sp.bwd_nb;
   }
-  // latency regime (forward mode 5, backward mode 4): one launch for forward +
-  // BPTT (lstm_sw_step_kernel); mode 4: the BPTT waves form dW on the matrix
-  // cores, one slab row per sequence, no dW launch
-  p.sw_step = p.sw && p.sw_fmode == 5 && p.sw_bmode == 4 && !s.stamps && s.sw_one_launch &&
-              pdrnn_lstm_sw_step_ok(NL, B, T) == 1;
-  p.sw_rdw = p.sw && p.sw_bmode == 4;
+  p.sw_step = p.sw && sp.one_launch && !s.stamps && s.sw_one_launch;
+  p.sw_rdw = p.sw && sp.register_dw;
   // Above one residency round the BPTT defers its weight gradients: the
   // recurrence writes the gate gradients (into `act`, in place) and the
   // matrix-core kernel lstm_small_dw forms dW / db over all B*T rows, one slab
@@ -1773,15 +1770,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "the sequence-in-wave kernels (lstm_sw.hip) cover this LSTM (cell 0) / GRU (cell 1) stack in the fused train step",
         py::arg("H"), py::arg("I"), py::arg("NL"), py::arg("cell") = 0);
   m.def("lstm_sw_step_ok", [](int64_t NL, int64_t B, int64_t T) {
-    return pdrnn_lstm_sw_step_ok((int)NL, (int)B, (int)T) == 1;
+    PdrnnLstmSwPlan sp{};
+    return pdrnn_lstm_sw_plan((int)NL, (int)B, (int)T, &sp) == 1 && sp.one_launch != 0;
   }, "the one-launch sequence-in-wave step (forward + BPTT in one kernel) covers this batch");
   m.def("lstm_sw_fits", [](int64_t NL, int64_t B, int64_t T) { return pdrnn_lstm_sw_fits((int)NL, (int)B, (int)T) == 1; },
         "every act / hseq row of this batch fits the sequence-in-wave kernels' 2 GiB buffer descriptor");
-  m.def("lstm_sw_mode", [](int64_t NL, int64_t B, bool backward) { return pdrnn_lstm_sw_mode((int)NL, (int)B, backward ? 1 : 0); },
-        "wave map of the sequence-in-wave kernels for B sequences (0/1: a wave per 1/2 sequences, 2/3: a wave "
-        "per layer of 1/2 sequences, 6: mode 2 at three waves per SIMD, forward only; 8: mode 6 with layer 1's "
-        "input projection on the matrix cores per 16-step chunk, the same bits, forward only)",
-        py::arg("NL"), py::arg("B"), py::arg("backward") = false);
+  m.def("lstm_sw_plan", [](int64_t NL, int64_t B, int64_t T, const optional<int64_t>& cus) {
+    PdrnnLstmSwPlan sp{};
+    const int ok = cus.has_value() ? pdrnn_lstm_sw_plan_cus((int)NL, (int)B, (int)T, (int)*cus, &sp)
+                                   : pdrnn_lstm_sw_plan((int)NL, (int)B, (int)T, &sp);
+    TORCH_CHECK(ok == 1, "the sequence-in-wave kernels do not serve NL=", NL, " B=", B, " T=", T);
+    py::dict d;
+    d["fwd_map"] = sp.fwd_map; d["bwd_map"] = sp.bwd_map; d["fwd_nb"] = sp.fwd_nb; d["bwd_nb"] = sp.bwd_nb;
+    d["one_launch"] = sp.one_launch != 0; d["register_dw"] = sp.register_dw != 0;
+    return d;
+  }, "the sequence-in-wave kernels' plan for B sequences of T steps: the wave map of each pass (the table in "
+     "lstm_sw.hip), its sequences per workgroup, whether one launch runs both passes and whether the backward "
+     "forms dW itself.  cus: plan for a device of that many compute units instead of the current one",
+        py::arg("NL"), py::arg("B"), py::arg("T"), py::arg("cus") = py::none());
   m.def("lstm_sw_fwd", &lstm_sw_fwd, "sequence-in-wave stack forward in one wave map -> (hseq, act, hn, cn)",
         py::arg("x"), py::arg("w"), py::arg("H"), py::arg("NL"), py::arg("mode"), py::arg("cell") = 0,
         py::arg("round_bf16") = false);

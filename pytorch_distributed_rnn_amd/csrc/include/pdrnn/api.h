@@ -60,7 +60,7 @@ typedef struct {
   // rows [B*T][xg_ld] for the deferred-dW kernel (NULL: not written)
   float* xg_out;
   int xg_ld;
-  // sequence-in-wave mode 5 with stamps: the phase-stamped build (stamps rows
+  // sequence-in-wave map 5 with stamps: the phase-stamped build (stamps rows
   // of 24: the loop stamps, then per-step cycle sums of waves 0 / 2)
   int phase_stamps;
 } PdrnnLstmSmallFwdArgs;
@@ -167,23 +167,32 @@ hipError_t pdrnn_lstm_small_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstm
 // ----------------------------------------------------------------------------
 // Sequence-in-wave LSTM / GRU stack (kernels/lstm_sw.hip): H = 32, 1 or 2
 // layers, input size <= 12, lean training contract (zero initial state, loss
-// through the fused head on h_T; the GRU as the packed 4-block stack, cell = 1).  A sequence's whole recurrence lives in ONE wave
-// (mode 0: one sequence per wave, mode 1: two), or in one wave per layer of a
-// 2-layer stack (mode 2), so h_t never crosses a workgroup barrier inside a
-// layer.  The forward writes act / hseq / xg_out like the gate-split forward
-// plus the head's slab rows; the backward writes the gate gradients over the
-// activations (dg_out = act, dg_st = 5H) for pdrnn_lstm_small_dw.
+// through the fused head on h_T; the GRU as the packed 4-block stack,
+// cell = 1).  A sequence's recurrence never leaves its wave (one layer), or
+// its layer's wave(s) (two layers), so h_t crosses no workgroup barrier inside
+// a layer.  How sequences and layers lie over waves is a wave map; the table
+// in lstm_sw.hip lists each map's passes, layer counts and geometry.  The
+// forward writes act / hseq / xg_out like the gate-split forward plus the
+// head's slab rows; the backward writes the gate gradients over the
+// activations (dg_out = act, dg_st = 5H) for pdrnn_lstm_small_dw, or with
+// register_dw forms the weight gradients itself, one slab row per workgroup.
 // ----------------------------------------------------------------------------
 int pdrnn_lstm_sw_ok(int H, int I, int NL, int cell);
 int pdrnn_lstm_sw_fits(int NL, int B, int T);
-// sequences per wave (and per workgroup) of a sequence-in-wave mode
-int pdrnn_lstm_sw_nb(int mode);
-// mode for a batch of B sequences (PDRNN_TUNE sw_mode / sw_bwd_mode override).
-// Forward mode 8 (layer 1's input projection on the matrix cores per 16-step
-// chunk) serves only the T that pdrnn_lstm_sw_fwd8_ok accepts: the caller
-// takes mode 6 otherwise.
-int pdrnn_lstm_sw_mode(int NL, int B, int backward);
-int pdrnn_lstm_sw_fwd8_ok(int NL, int T);
+// Which map runs each pass of B sequences of T steps (the CU thresholds, the
+// PDRNN_TUNE sw_mode / sw_bwd_mode overrides, the maps' rules on T).  Returns
+// 0 where the family does not serve the batch.  _cus: for a device of `cus`
+// compute units instead of the current one.
+typedef struct {
+  int fwd_map, bwd_map;  // the `mode` of pdrnn_lstm_sw_fwd / _bwd
+  int fwd_nb, bwd_nb;    // sequences per workgroup: grid = ceil(B / nb)
+  int one_launch;        // pdrnn_lstm_sw_step runs both passes
+  int register_dw;       // the backward needs no pdrnn_lstm_small_dw launch
+} PdrnnLstmSwPlan;
+int pdrnn_lstm_sw_plan(int NL, int B, int T, PdrnnLstmSwPlan* plan);
+int pdrnn_lstm_sw_plan_cus(int NL, int B, int T, int cus, PdrnnLstmSwPlan* plan);
+// hipErrorInvalidValue for a map the table does not list for the pass and
+// layer count, or that does not run this T
 hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t stream);
 hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t stream);
 
@@ -251,10 +260,9 @@ typedef struct {
 } PdrnnAdamArgs;
 hipError_t pdrnn_adam_flat(const PdrnnAdamArgs* a, hipStream_t stream);
 
-// One launch per training step in the latency regime (two layers, B <= two
-// workgroups per CU, T % 4 == 0): forward mode 5 + head/CE, then BPTT mode 4
-// with its matrix-core dW waves (kernels/lstm_sw.hip lstm_sw_step_kernel).
-int pdrnn_lstm_sw_step_ok(int NL, int B, int T);
+// One launch per training step where the plan says one_launch (two layers,
+// B <= two workgroups per CU, T % 4 == 0): forward map 5 + head/CE, then BPTT
+// map 4 with its matrix-core dW waves (kernels/lstm_sw.hip lstm_sw_step_kernel).
 hipError_t pdrnn_lstm_sw_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b, hipStream_t stream);
 // g *= min(1, max_norm / (||g|| + eps)) with no host sync; work: [nparts]
 // floats (nparts <= 1024 partial sums of squares), out: [2] = (scale, norm).

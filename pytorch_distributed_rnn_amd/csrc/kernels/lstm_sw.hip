@@ -22,9 +22,9 @@
 //    DPP swaps give both lanes all four gates; both update c, h.
 //  * h_t goes to a per-wave LDS slot and is read back by the same wave next
 //    step: LDS operations of one wave execute in order, so no barrier and no
-//    waitcnt beyond the reads' own.  Mode 2 runs each layer of a 2-layer
-//    stack in its own wave (one barrier per step, h^0 handed over through
-//    parity slots) for the latency regime.
+//    waitcnt beyond the reads' own.  A two-layer stack runs each layer in
+//    its own wave (one barrier per step, h^0 handed over through parity
+//    slots).
 //  * BPTT, per layer: lane (u, s) owns column u of W_hh (and W_ih for
 //    layers >= 1: the input gradient feeding the layer below) over gate rows
 //    [64 s, 64 s + 64); the row phase makes the lane's two pre-activation gate
@@ -32,9 +32,11 @@
 //    them to LDS and over the activation slots (deferred dW, lstm_small_dw.hip),
 //    and the column phase reads its 64 rows back (16 ds_read_b128) for
 //    W^T dz; one DPP swap completes the sums.  Layer 1's input gradient
-//    stays in registers for layer 0's next step (mode 2: LDS parity slots).
-//  * Whole sequences per wave, so the grid is B / NB waves, at most one wave
-//    per SIMD (~300-400 VGPRs: every weight in registers).
+//    reaches layer 0's wave through LDS parity slots.
+//  * How sequences and layers lie over waves is a WAVE MAP: the table kMaps
+//    below holds one row per map id, and every kernel constant, launch
+//    geometry and planner rule reads it.  pdrnn_lstm_sw_plan picks the maps
+//    of a batch (docs/DESIGN.md §2b).
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"
 #include "pdrnn/motion_head.h"
@@ -76,11 +78,59 @@ PDRNN_DEVICE int pick(const int (&v)[NB], int n) {
   else if constexpr (NB == 2) return n == 0 ? v[0] : v[1];
   else return n == 0 ? v[0] : n == 1 ? v[1] : v[2];
 }
-// sequences per wave of a mode: 1 (0, 2, 4, 5, 6, 8), 2 (1, 3).  (Three per
-// layer wave -- the mode-2 map at 960 waves for B = 1440, one per SIMD --
-// measured slower in both passes: forward +28 us, BPTT +20 us against modes
-// 6 / 3, profiles/r6/m7_ab.md; removed.)
-constexpr int sw_nb(int mode) { return (mode == 1 || mode == 3) ? 2 : 1; }
+
+// ---------------------------------------------------------------------------
+// Wave maps: how sequences and layers are laid over waves.  One row per map
+// id (the `mode` of pdrnn_lstm_sw_fwd / _bwd, PDRNN_TUNE sw_mode /
+// sw_bwd_mode); everything that is a property of the map is read from here --
+// the kernels' template constants, __launch_bounds__, the launchers' grid,
+// block and LDS, the planner's override check.  A map serves only the passes
+// and layer counts its row lists.
+//   0 / 1  one layer: a wave runs 1 / 2 whole sequences.
+//   2      two layers, wave l runs layer l of one sequence; one barrier per
+//          step (h^0_t / the input gradient handed over through parity slots).
+//   3      backward of map 2 with two sequences per layer wave.
+//   4      backward of map 2 plus two waves that accumulate the weight
+//          gradients on the matrix cores (register dW: no gate-gradient
+//          stores, no dW launch; an 8-slot dz ring holds a 4-step K step).
+//   5      forward, four waves per sequence (lstm_sw_fwd4_kernel).
+//   6      forward of map 2 capped at 168 VGPRs: three waves per SIMD.
+//   8      map 6 with layer 1's input projection on the matrix cores per
+//          16-step chunk (lstm_sw_fwd8_kernel), the same bits.
+// (Removed, measured slower: 7, three sequences per layer wave -- forward
+// +28 us, BPTT +20 us against 6 / 3 at B = 1440, profiles/r6/m7_ab.md; both
+// layers of a two-layer stack in one wave, maps 0 / 1 / forward 3 at NL = 2 --
+// forward 117.4 vs 68.2 us and backward 165.7 vs 53.2 us at B = 180 against
+// map 2, profiles/r5/sw/sw1_probe.log.)
+// ---------------------------------------------------------------------------
+struct WaveMap {
+  bool fwd, bwd;     // passes served
+  bool nl1, nl2;     // layer counts served
+  int nb;            // sequences per wave (= per workgroup)
+  bool split;        // each layer in waves of its own
+  int waves;         // waves per workgroup
+  int eu_cap;        // amdgpu_waves_per_eu of the forward kernels (3: <= 168 VGPRs; 1: uncapped)
+  bool rdw;          // register dW: two more waves on the matrix cores
+  int zr;            // dz ring slots per (sequence, layer), backward
+  int t_mult;        // T must be a multiple of this
+};
+constexpr int kNumMaps = 9;
+constexpr WaveMap kMaps[kNumMaps] = {
+    //       fwd    bwd    nl1    nl2    nb split  waves eu rdw    zr  t_mult
+    /* 0 */ {true,  true,  true,  false, 1, false, 1,    1, false, 2,  1},
+    /* 1 */ {true,  true,  true,  false, 2, false, 1,    1, false, 2,  1},
+    /* 2 */ {true,  true,  false, true,  1, true,  2,    1, false, 2,  1},
+    /* 3 */ {false, true,  false, true,  2, true,  2,    1, false, 2,  1},
+    /* 4 */ {false, true,  false, true,  1, true,  4,    1, true,  8,  4},
+    /* 5 */ {true,  false, false, true,  1, true,  4,    1, false, 0,  1},
+    /* 6 */ {true,  false, false, true,  1, true,  2,    3, false, 0,  1},
+    /* 7 */ {false, false, false, false, 1, false, 1,    1, false, 0,  1},  // (removed)
+    /* 8 */ {true,  false, false, true,  1, true,  2,    3, false, 0,  16},
+};
+constexpr bool map_serves(int map, bool backward, int NL) {
+  return map >= 0 && map < kNumMaps && (backward ? kMaps[map].bwd : kMaps[map].fwd) &&
+         (NL == 1 ? kMaps[map].nl1 : NL == 2 && kMaps[map].nl2);
+}
 
 // ---------------------------------------------------------------------------
 // Forward
@@ -219,6 +269,31 @@ PDRNN_DEVICE Cell fwd_cell_any(const float (&p)[4], pdrnn_f2 gk, float c, float 
   if constexpr (CELL == 0) return fwd_cell(p, gk, c, odd);
   else return fwd_cell_gru(p, hprev, odd);
 }
+// The saved rows of a step: this lane's two activations and the unit's c to
+// row `rw` of act (5H floats a row), h to hseq.  `m`: kOOR drops the stores.
+PDRNN_DEVICE void store_cell(const Cell& r, __amdgpu_buffer_rsrc_t r_act, __amdgpu_buffer_rsrc_t r_h, uint32_t vo_a0,
+                             uint32_t vo_a1, uint32_t vo_c, uint32_t vo_h, uint32_t m, uint32_t rw) {
+  bstore(r.a0, r_act, vo_a0 | m, rw * (5 * kH * 4));
+  bstore(r.a1, r_act, vo_a1 | m, rw * (5 * kH * 4));
+  bstore(r.c, r_act, vo_c | m, rw * (5 * kH * 4));
+  bstore(r.h, r_h, vo_h | m, rw * (kH * 4));
+}
+
+// Per-workgroup stamps (PDRNN_LSTM_STAMPS), thread 0, a row of a.stamps:
+// [0] / [1] the cycle counter at the loop's start / end, [2] / [3] real time
+// there, [4] / [5] real time at kernel entry / exit, [6] the CU.
+PDRNN_DEVICE uint64_t stamp_entry(const uint64_t* stamps, int tid) { return (stamps && tid == 0) ? stamp_real() : 0; }
+PDRNN_DEVICE void stamp_loop_begin(const uint64_t* stamps, int tid, uint64_t& st0, uint64_t& sr0) {
+  st0 = 0; sr0 = 0;
+  if (stamps && tid == 0) { st0 = stamp_cycles(); sr0 = stamp_real(); }
+}
+PDRNN_DEVICE void stamp_loop_end(uint64_t* st, uint64_t st0, uint64_t sr0) {
+  st[0] = st0; st[1] = stamp_cycles(); st[2] = sr0; st[3] = stamp_real();
+}
+PDRNN_DEVICE void stamp_exit(uint64_t* st, uint64_t sr_in) {
+  st[4] = sr_in; st[5] = stamp_real(); st[6] = stamp_cu();
+}
+
 template <int NL, int NB>
 PDRNN_DEVICE constexpr int fwd_lds_floats_hb() { return NB * NL * 2 * kHB; }
 
@@ -289,22 +364,20 @@ PDRNN_DEVICE bool stage_x_vec(const PdrnnLstmSmallFwdArgs& a, float* xs, const i
   return true;
 }
 
-// NL = 1 or 2.  MODE 0/1: one wave runs all layers of NB = 1 / 2 sequences.
-// MODE 2/3 (NL = 2): wave l runs layer l of NB = 1 / 2 sequences, one
-// barrier per step (layer 0's h_t handed over through parity slots).
-// mode 2 holds <= 168 VGPRs: three waves per SIMD, so B = 1440 (2880 layer
-// waves on 1024 SIMDs) is one residency round with every SIMD loaded evenly
+// Maps 0 / 1 (one layer) and 2 / 6 (two layers, a wave per layer).  Map 6
+// holds <= 168 VGPRs: three waves per SIMD, so B = 1440 (2880 layer waves on
+// 1024 SIMDs) is one residency round with every SIMD loaded evenly.
 template <int NL, int MODE, int CELL = 0>
-__global__ void __launch_bounds__(MODE >= 2 ? 64 * NL : 64) __attribute__((amdgpu_waves_per_eu(MODE == 6 ? 3 : 1)))
+__global__ void __launch_bounds__(64 * kMaps[MODE].waves) __attribute__((amdgpu_waves_per_eu(kMaps[MODE].eu_cap)))
 lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
-  constexpr int NB = sw_nb(MODE);
-  constexpr bool SPLIT = MODE >= 2;
-  static_assert(NL == 1 || NL == 2, "one or two layers");
-  static_assert(!SPLIT || NL == 2, "layer-split mode needs two layers");
+  constexpr int NB = kMaps[MODE].nb;
+  constexpr bool SPLIT = kMaps[MODE].split;
+  static_assert(map_serves(MODE, false, NL), "the wave map table lists no such forward");
+  static_assert(SPLIT == (NL == 2), "one layer per wave");
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const uint64_t sr_in = (a.stamps && tid == 0) ? stamp_real() : 0;  // (entry: the prologue's cost)
+  const uint64_t sr_in = stamp_entry(a.stamps, tid);  // (the prologue's cost)
   const int lane = tid & 63;
   const int wv = SPLIT ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;
   const int u = lane >> 1;
@@ -329,7 +402,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   // ---- prologue: zero the h slots (h_{-1} = 0, pad chunks), stage x ------
   // (the vector staging writes only the I real columns: xs zeroed first; two
   // sequences per workgroup only -- with one, the zeroing pass and barrier
-  // cost more than the element loads: mode 6 136.2 vs 133.6 us at B = 1440)
+  // cost more than the element loads: map 6 136.2 vs 133.6 us at B = 1440)
   const bool xvec = NB == 2 && a.x_st == I && a.x_sb == (int64_t)T * I;
   for (int e = tid; e < fwd_lds_floats_hb<NL, NB>() + (xvec ? NB * T * kXS : 0); e += nthr) hb[e] = 0.f;
   if (xvec) lds_barrier();
@@ -387,9 +460,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
 
   // Layer 0 at time t (active unless t == T) / layer 1 at time t (active
   // unless t < 0), for all NB sequences, split into the operand reads and the
-  // rest: a caller running both layers issues both layers' reads first (their
-  // LDS order against the other layer's h write would otherwise serialise
-  // the two independent chains).
+  // rest (the uncapped maps pin every read ahead of the first FMA).
   auto rd0 = [&](int t, float4 (&v)[NB][6]) {
     const int tc = min(t, T - 1);
 #pragma unroll
@@ -416,11 +487,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
     hst[l][n] = act ? r.h : hst[l][n];
     hbuf(n, l, t & 1)[u] = hst[l][n];
     const uint32_t rw = row(l, n, min(max(t, 0), T - 1));
-    const uint32_t m = act ? vmask[n] : kOOR;
-    bstore(r.a0, r_act, vo_a0 | m, rw * (5 * kH * 4));
-    bstore(r.a1, r_act, vo_a1 | m, rw * (5 * kH * 4));
-    bstore(r.c, r_act, vo_c | m, rw * (5 * kH * 4));
-    bstore(r.h, r_h, vo_h | m, rw * (kH * 4));
+    store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, act ? vmask[n] : kOOR, rw);
   };
   const pdrnn_f2 gk = odd ? pdrnn_f2{1.f, 0.f} : pdrnn_f2{2.f, -1.f};
   auto cmp0 = [&](const FwdW<6>& W, int t, const float4 (&v)[NB][6]) {
@@ -447,29 +514,18 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
       rd0(t, v0);
       cmp0(W0, t, v0);
     }
-  } else if constexpr (!SPLIT) {
-    const FwdW<6> W0 = load_fwd_w<6, CELL>(a, 0, u, odd ? 1 : 0);
-    const FwdW<8> W1 = load_fwd_w<8, CELL>(a, 1, u, odd ? 1 : 0);
-    // layer 0 at t = it, layer 1 at t = it - 1: both read h^0_{it-1}
-    for (int it = 0; it <= T; ++it) {
-      float4 v0[NB][6], v1[NB][8];
-      rd0(it, v0);
-      rd1(it - 1, v1);
-      cmp0(W0, it, v0);
-      cmp1(W1, it - 1, v1);
-    }
   } else {
-    // mode 2: every operand read of the step in flight before the first
-    // FMA (one LDS latency per step); mode 6 (the same map at <= 168 VGPRs,
-    // three waves per SIMD for B > one wave per SIMD) leaves the reads to the
-    // scheduler, which pairs them to stay within its registers
+    // uncapped: every operand read of the step in flight before the first
+    // FMA (one LDS latency per step); under the register cap the reads are
+    // left to the scheduler, which pairs them to stay within its registers
+    constexpr bool PIN_READS = kMaps[MODE].eu_cap == 1;
     if (wv == 0) {
       const FwdW<6> W0 = load_fwd_w<6, CELL>(a, 0, u, odd ? 1 : 0);
       for (int it = 0; it <= T; ++it) {
         if (it < T) {
           float4 v0[NB][6];
           rd0(it, v0);
-          if constexpr (MODE != 6) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (PIN_READS) __builtin_amdgcn_sched_barrier(0);
           cmp0(W0, it, v0);
         }
         lds_barrier();
@@ -480,7 +536,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
         if (it > 0) {
           float4 v1[NB][8];
           rd1(it - 1, v1);
-          if constexpr (MODE != 6) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (PIN_READS) __builtin_amdgcn_sched_barrier(0);
           cmp1(W1, it - 1, v1);
         }
         lds_barrier();
@@ -497,7 +553,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   // ---- epilogue: h_n / c_n, then the fused head on the top layer's h_T ----
   // (two sequences per wave: both heads' operands loaded first, their
   // dependent loads in flight together, not behind the first head's stores;
-  // one sequence loads inline -- the VGPR-capped mode 6 would spill)
+  // one sequence loads inline -- the VGPR-capped map 6 would spill)
   const bool top_wave = !SPLIT || wv == NL - 1;
   HeadIn hin[NB];
   if constexpr (NB > 1) {
@@ -521,24 +577,21 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
       else motion_head(a, b, hst[NL - 1][n], u, odd);
     }
   }
-  if (a.stamps && tid == 0) {
-    uint64_t* st = a.stamps + (uint64_t)blockIdx.x * 8;
-    st[4] = sr_in; st[5] = stamp_real(); st[6] = stamp_cu();
-  }
+  if (a.stamps && tid == 0) stamp_exit(a.stamps + (uint64_t)blockIdx.x * 8, sr_in);
 }
 
 // ---------------------------------------------------------------------------
-// Forward, four waves per sequence (mode 5, two-layer stacks in the latency
+// Forward, four waves per sequence (map 5, two-layer stacks in the latency
 // regime): wave w runs layer w >> 1, units 16 (w & 1) .. + 15.  lane =
 // (unit ul = lane >> 2, K quarter q = lane & 3): a lane holds the four gate
 // rows of its unit over a quarter of the operand vector (layer 0: x | h[0,12)
 // | h[12,24) | h[24,32) + zero pad, 3 float4 chunks; layer 1: h^0[0,16) |
-// h^0[16,32) | h^1[0,16) | h^1[16,32), 4 chunks), half of mode 2's products
+// h^0[16,32) | h^1[0,16) | h^1[16,32), 4 chunks), half of map 2's products
 // per lane.  A quad reduce-scatter (xor 2, then xor 1) leaves lane q with the
 // full pre-activation of gate q (i, f, g, o): one activation per lane; quad
 // broadcasts give every lane of the unit i, f, g, o for c and h.  The two
 // waves of a layer meet in the per-layer h slots: one barrier per step, as in
-// mode 2.
+// map 2.
 // ---------------------------------------------------------------------------
 template <int NC>
 struct Fwd4W {
@@ -605,7 +658,7 @@ template <int CELL = 0, bool PH = false>
 PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
-  const uint64_t sr_in = (a.stamps && tid == 0) ? stamp_real() : 0;  // (entry: the prologue's cost)
+  const uint64_t sr_in = stamp_entry(a.stamps, tid);  // (the prologue's cost)
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l = wv >> 1;
@@ -641,8 +694,8 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   const pdrnn_f2 gk = q == 2 ? pdrnn_f2{2.f, -1.f} : pdrnn_f2{1.f, 0.f};
   float cst = 0.f, hst = 0.f;
 
-  uint64_t st0 = 0, sr0 = 0;
-  if (a.stamps && tid == 0) { st0 = stamp_cycles(); sr0 = stamp_real(); }
+  uint64_t st0, sr0;
+  stamp_loop_begin(a.stamps, tid, st0, sr0);
 
   // quad reduce-scatter of the four gate partials -> this lane's gate (q)
   auto gate_sum = [&](const float (&p)[4]) {
@@ -781,7 +834,7 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   }
   if (a.stamps && tid == 0) {
     uint64_t* st = a.stamps + (uint64_t)blockIdx.x * (PH ? 24 : 8);
-    st[0] = st0; st[1] = stamp_cycles(); st[2] = sr0; st[3] = stamp_real();
+    stamp_loop_end(st, st0, sr0);
     st[4] = sr_in; st[6] = stamp_cu();  // (exit: after the head, below)
   }
   if constexpr (PH) {
@@ -808,15 +861,15 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   if (a.stamps && tid == 0) a.stamps[(uint64_t)blockIdx.x * (PH ? 24 : 8) + 5] = stamp_real();
 }
 template <int CELL, bool PH = false>
-__global__ void __launch_bounds__(256) lstm_sw_fwd4_kernel(PdrnnLstmSmallFwdArgs a) { fwd4_body<CELL, PH>(a); }
+__global__ void __launch_bounds__(64 * kMaps[5].waves) lstm_sw_fwd4_kernel(PdrnnLstmSmallFwdArgs a) { fwd4_body<CELL, PH>(a); }
 
 // ---------------------------------------------------------------------------
-// Forward, layer 1's input projection hoisted onto the matrix cores (mode 8,
-// two-layer stacks in the throughput regime, T % 16 == 0).  Mode 6's waves
+// Forward, layer 1's input projection hoisted onto the matrix cores (map 8,
+// two-layer stacks in the throughput regime, T % 16 == 0).  Map 6's waves
 // (wave l = layer l of one sequence, <= 168 VGPRs: three waves per SIMD), and
-// BIT FOR BIT mode 6's results: every gate pre-activation is the same sum of
+// BIT FOR BIT map 6's results: every gate pre-activation is the same sum of
 // the same fp32 operations, only computed elsewhere.
-//  * Mode 6 forms a gate of layer 1 as (in.x + in.y) + (rec.x + rec.y): `in`
+//  * Map 6 forms a gate of layer 1 as (in.x + in.y) + (rec.x + rec.y): `in`
 //    the v_pk_fma_f32 chain over the input h^0_t (.x the even columns in
 //    ascending order, .y the odd ones; seeded with the bias for i, g) and
 //    `rec` the same over the own h_{t-1} (seeded with the bias for f, o).
@@ -834,7 +887,7 @@ __global__ void __launch_bounds__(256) lstm_sw_fwd4_kernel(PdrnnLstmSmallFwdArgs
 //    of 64, no K-split DPP adds -- and adds its two P values (one ds_read_b64:
 //    P column 4u + 2s + j is gate row (s + 2j) H + u; row stride kPS = 132
 //    keeps the C tile's rows 4g + r on disjoint banks).
-//  * Layer 0 runs mode 6's step unchanged (its x columns share a chain with
+//  * Layer 0 runs map 6's step unchanged (its x columns share a chain with
 //    h[0, 12), so they cannot leave it without changing the sum) and also
 //    writes h^0_t into a ring of 2 chunks x 16 rows; the layer-1 wave runs one
 //    chunk behind and reads a chunk of h^0 as its A fragments: one workgroup
@@ -852,12 +905,13 @@ PDRNN_DEVICE float gate_scale(int q) { return kA * ((CELL == 0 ? q == 2 : q >= 2
 // gate row of P column p (see above)
 PDRNN_DEVICE int p_row(int p) { return (((p >> 1) & 1) + 2 * (p & 1)) * kH + (p >> 2); }
 
+static_assert(kMaps[8].t_mult == kCT && kMaps[8].waves == 2, "map 8: whole chunks, a wave per layer");
 template <int CELL>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3)))
+__global__ void __launch_bounds__(64 * kMaps[8].waves) __attribute__((amdgpu_waves_per_eu(kMaps[8].eu_cap)))
 lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
-  const uint64_t sr_in = (a.stamps && tid == 0) ? stamp_real() : 0;  // (entry: the prologue's cost)
+  const uint64_t sr_in = stamp_entry(a.stamps, tid);  // (the prologue's cost)
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // = layer
   const int u = lane >> 1, s = lane & 1;
@@ -922,10 +976,7 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
     hst = r.h;
     hs[(t & 1) * kHB + u] = r.h;
     const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((wv * B + b) * T + t));
-    bstore(r.a0, r_act, vo_a0, rw * (5 * kH * 4));
-    bstore(r.a1, r_act, vo_a1, rw * (5 * kH * 4));
-    bstore(r.c, r_act, vo_c, rw * (5 * kH * 4));
-    bstore(r.h, r_h, vo_h, rw * (kH * 4));
+    store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, 0u, rw);
   };
 
   if (wv == 0) {
@@ -1029,19 +1080,13 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
       lds_barrier();
     }
   }
-  if (a.stamps && tid == 0) {
-    uint64_t* st = a.stamps + (uint64_t)blockIdx.x * 8;
-    st[0] = st0; st[1] = stamp_cycles(); st[2] = sr0; st[3] = stamp_real();
-  }
+  if (a.stamps && tid == 0) stamp_loop_end(a.stamps + (uint64_t)blockIdx.x * 8, st0, sr0);
 
   // ---- epilogue: h_n / c_n, then the fused head on the top layer's h_T ----
   if (!odd && a.hn) a.hn[((int64_t)wv * B + b) * kH + u] = hst;
   if (!odd && a.cn) a.cn[((int64_t)wv * B + b) * kH + u] = cst;
   if (a.head_w && wv == 1) motion_head(a, b, hst, u, odd);
-  if (a.stamps && tid == 0) {
-    uint64_t* st = a.stamps + (uint64_t)blockIdx.x * 8;
-    st[4] = sr_in; st[5] = stamp_real(); st[6] = stamp_cu();
-  }
+  if (a.stamps && tid == 0) stamp_exit(a.stamps + (uint64_t)blockIdx.x * 8, sr_in);
 }
 
 // ---------------------------------------------------------------------------
@@ -1113,22 +1158,20 @@ PDRNN_DEVICE float col_dot(const BwdCol& W, const float4 (&g)[16]) {
 // runs at B <= one wave per SIMD)
 template <int NL, int MODE, int CELL = 0>
 PDRNN_DEVICE void bwd_body(const PdrnnLstmSmallBwdArgs& a) {
-  constexpr int NB = sw_nb(MODE);
-  constexpr bool SPLIT = MODE >= 2;
-  // mode 4: the mode-2 map plus two waves that accumulate the weight
-  // gradients on the matrix cores (no gate-gradient stores, no dW launch).
   // (A four-wave BPTT map -- two waves per layer, unit x row quarter -- was
   // correct but slower: 92.7 vs 55.3 us at B = 180, the column phase waiting
   // behind the barrier for the other wave's dz; profiles/r5/sw/bwd5_probe.log;
   // removed in round 6.)
-  constexpr bool DWACC = MODE == 4;
-  constexpr int ZR = DWACC ? 8 : 2;  // dz slots per (sequence, layer): a ring that holds a dW K step
-  static_assert(NL == 1 || NL == 2, "one or two layers");
-  static_assert(!SPLIT || NL == 2, "layer-split mode needs two layers");
+  constexpr int NB = kMaps[MODE].nb;
+  constexpr bool SPLIT = kMaps[MODE].split;
+  constexpr bool DWACC = kMaps[MODE].rdw;
+  constexpr int ZR = kMaps[MODE].zr;
+  static_assert(map_serves(MODE, true, NL), "the wave map table lists no such backward");
+  static_assert(SPLIT == (NL == 2), "one layer per wave");
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
   const int tid = threadIdx.x;
-  const uint64_t sr_in = (a.stamps && tid == 0) ? stamp_real() : 0;  // (entry: the prologue's cost)
+  const uint64_t sr_in = stamp_entry(a.stamps, tid);  // (the prologue's cost)
   const int lane = tid & 63;
   const int wv = SPLIT ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;
   const int u = lane >> 1;
@@ -1137,7 +1180,7 @@ PDRNN_DEVICE void bwd_body(const PdrnnLstmSmallBwdArgs& a) {
   const int B = a.B, T = a.T;
   const int bbase = blockIdx.x * NB;
   float* dzb = smem;                          // [NB][NL][ZR][kDZ]
-  float* dxb = smem + NB * NL * ZR * kDZ;     // [NB][2][32] (modes 2/3: layer 1 -> layer 0)
+  float* dxb = smem + NB * NL * ZR * kDZ;     // [NB][2][32] (layer 1's input gradient -> layer 0)
   auto dzbuf = [&](int n, int l, int t) { return dzb + ((n * NL + l) * ZR + (t & (ZR - 1))) * kDZ; };
 
   int bidx[NB];
@@ -1194,23 +1237,20 @@ PDRNN_DEVICE void bwd_body(const PdrnnLstmSmallBwdArgs& a) {
   };
 
   // per (layer, sequence) state
-  float dhrec[NL][NB], dc[NL][NB], dx1[NB];
+  float dhrec[NL][NB], dc[NL][NB];
 #pragma unroll
   for (int l = 0; l < NL; ++l)
 #pragma unroll
     for (int n = 0; n < NB; ++n) { dhrec[l][n] = 0.f; dc[l][n] = 0.f; }
   float dhtop[NB];
 #pragma unroll
-  for (int n = 0; n < NB; ++n) {
-    dx1[n] = 0.f;
-    dhtop[n] = a.dhn[(int64_t)bidx[n] * kH + u];
-  }
+  for (int n = 0; n < NB; ++n) dhtop[n] = a.dhn[(int64_t)bidx[n] * kH + u];
   if (SPLIT) {
     for (int e = tid; e < NB * 2 * 32; e += blockDim.x) dxb[e] = 0.f;
   }
 
-  uint64_t st0 = 0, sr0 = 0;
-  if (a.stamps && tid == 0) { st0 = stamp_cycles(); sr0 = stamp_real(); }
+  uint64_t st0, sr0;
+  stamp_loop_begin(a.stamps, tid, st0, sr0);
 
   // Iteration `it`: the top layer at t = T-1-it, layer 0 (of a 2-layer stack)
   // at t = T-it (lag 1: its dh input is layer 1's input gradient of step t).
@@ -1416,50 +1456,8 @@ PDRNN_DEVICE void bwd_body(const PdrnnLstmSmallBwdArgs& a) {
       body(it + 1, opB);
     }
     if (it < iters) body(it, opA);
-  } else if constexpr (!SPLIT) {
-    const BwdCol Whh1 = load_bwd_col(a.w_hh[1], kH, u, true, u, s, a.w_bf16);
-    const BwdCol Wih1 = load_bwd_col(a.w_ih[1], kH, u, true, u, s, a.w_bf16);
-    const BwdCol Whh0 = load_bwd_col(a.w_hh[0], kH, u, true, u, s, a.w_bf16);
-    Ops opA[2][NB], opB[2][NB];
-    // issue order pinned (A's loads, then B's, each layer 1 then layer 0): the
-    // loop's counted vmcnt waits are the max over its entry edges
-#pragma unroll
-    for (int n = 0; n < NB; ++n) { opA[1][n] = load_ops(1, n, T - 1); opA[0][n] = load_ops(0, n, T); }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) { opB[1][n] = load_ops(1, n, T - 2); opB[0][n] = load_ops(0, n, T - 1); }
-    __builtin_amdgcn_sched_barrier(0);
-    auto body = [&](int it, Ops (&op)[2][NB]) {
-      const int t1 = T - 1 - it, t0 = T - it;
-      const bool act1 = t1 >= 0, act0 = t0 < T;
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        rows(1, n, t1, op[1][n], it == 0 ? dhtop[n] : 0.f, act1);
-        rows(0, n, t0, op[0][n], dx1[n], act0);
-      }
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        float4 g1[16], g0[16];
-        read_dz(1, n, t1, g1);
-        read_dz(0, n, t0, g0);
-        const float vh1 = col_dot(Whh1, g1);
-        const float vx1 = col_dot(Wih1, g1);
-        const float vh0 = col_dot(Whh0, g0);
-        dhrec[1][n] = act1 ? vh1 : dhrec[1][n];
-        dx1[n] = act1 ? vx1 : 0.f;
-        dhrec[0][n] = act0 ? vh0 : dhrec[0][n];
-      }
-#pragma unroll
-      for (int n = 0; n < NB; ++n) { op[1][n] = load_ops(1, n, t1 - 2); op[0][n] = load_ops(0, n, t0 - 2); }
-    };
-    int it = 0;
-    for (; it + 1 < iters; it += 2) {
-      body(it, opA);
-      body(it + 1, opB);
-    }
-    if (it < iters) body(it, opA);
   } else {
-    // modes 2/3: wave 1 = layer 1 (t = T-1-it), wave 0 = layer 0 (t = T-it),
+    // wave 1 = layer 1 (t = T-1-it), wave 0 = layer 0 (t = T-it),
     // one barrier per iteration; layer 1's input gradient of step t reaches
     // layer 0 through dxb[n][t & 1]
     if (wv == 1) {
@@ -1551,16 +1549,16 @@ PDRNN_DEVICE void bwd_body(const PdrnnLstmSmallBwdArgs& a) {
   }
 }
 template <int NL, int MODE, int CELL = 0>
-__global__ void __launch_bounds__(MODE == 4 ? 256 : MODE >= 2 ? 64 * NL : 64)
+__global__ void __launch_bounds__(64 * kMaps[MODE].waves)
 lstm_sw_bwd_kernel(PdrnnLstmSmallBwdArgs a) {
   bwd_body<NL, MODE, CELL>(a);
 }
 
 // ---------------------------------------------------------------------------
 // One-launch step (latency regime: B <= two workgroups per CU, two layers).
-// Workgroup b runs sequence b's four-wave forward (mode 5) with the head/CE,
+// Workgroup b runs sequence b's four-wave forward (map 5) with the head/CE,
 // then -- no grid-wide dependency between the passes -- the same sequence's
-// BPTT with its two matrix-core dW waves (mode 4): each sequence's backward
+// BPTT with its two matrix-core dW waves (map 4): each sequence's backward
 // starts the moment its own forward ends instead of after the slowest
 // workgroup of a forward launch.  Every operand the backward reads (act,
 // hseq, the staged x rows, dh_T) was written by the same workgroup: a
@@ -1571,11 +1569,12 @@ lstm_sw_bwd_kernel(PdrnnLstmSmallBwdArgs a) {
 // the coherent stores 35 (profiles/r6/one_launch_step.md).
 // ---------------------------------------------------------------------------
 template <int CELL>
-__global__ void __launch_bounds__(256) lstm_sw_step_kernel(PdrnnLstmSmallFwdArgs f, PdrnnLstmSmallBwdArgs bk) {
+__global__ void __launch_bounds__(64 * kMaps[4].waves) lstm_sw_step_kernel(PdrnnLstmSmallFwdArgs f, PdrnnLstmSmallBwdArgs bk) {
   fwd4_body<CELL>(f);
   __syncthreads();  // the forward's outputs (act, hseq, x rows, dh_T) before the backward reads them
   bwd_body<2, 4, CELL>(bk);
 }
+static_assert(kMaps[5].waves == kMaps[4].waves, "the one-launch step runs both maps in one workgroup");
 
 // ---- host side -------------------------------------------------------------
 int sw_cus() {
@@ -1591,59 +1590,99 @@ int sw_cus() {
   return c_val;
 }
 
-size_t fwd_lds(int NL, int nb, int T) { return sizeof(float) * ((size_t)nb * NL * 2 * kHB + (size_t)nb * T * kXS); }
-size_t bwd_lds(int NL, int nb, int zr = 2) { return sizeof(float) * ((size_t)nb * NL * zr * kDZ + (size_t)nb * 2 * 32); }
-int mode_nb(int mode) { return sw_nb(mode); }
+// Dynamic LDS of a launch.  Forward: the h parity slots and the staged x rows
+// of the workgroup's sequences (map 8: its P tile, ring, slots and seeds).
+// Backward: the dz rings and the input-gradient parity slots.
+size_t fwd_lds(int map, int NL, int T) {
+  if (map == 8) return sizeof(float) * ((size_t)kF8X + (size_t)T * kXS);
+  const size_t nb = kMaps[map].nb;
+  return sizeof(float) * (nb * NL * 2 * kHB + nb * T * kXS);
+}
+size_t bwd_lds(int map, int NL) {
+  const size_t nb = kMaps[map].nb;
+  return sizeof(float) * (nb * NL * kMaps[map].zr * kDZ + nb * 2 * 32);
+}
+size_t step_lds(int T) { return std::max(fwd_lds(5, 2, T), bwd_lds(4, 2)); }
 
-template <int NL, int MODE>
-hipError_t launch_fwd(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  constexpr int NB = sw_nb(MODE);
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = MODE >= 2 ? 64 * NL : 64;
-  if (a->cell == 1)
-    hipLaunchKernelGGL((lstm_sw_fwd_kernel<NL, MODE, 1>), dim3(grid), dim3(block), fwd_lds(NL, NB, a->T), st, *a);
-  else
-    hipLaunchKernelGGL((lstm_sw_fwd_kernel<NL, MODE, 0>), dim3(grid), dim3(block), fwd_lds(NL, NB, a->T), st, *a);
+// The sequence lengths a map runs: whole K steps / chunks, and for map 8
+// (14,144 bytes of LDS plus 48 T of x rows) six workgroups -- three waves per
+// SIMD -- in a CU's 160 KiB, 26,624 bytes each in 2 KiB granules: T <= 256.
+bool map_serves_T(int map, int NL, int T) {
+  if (T <= 0 || T % kMaps[map].t_mult) return false;
+  return map != 8 || 6 * ((fwd_lds(8, NL, T) + 2047) / 2048 * 2048) <= 160 * 1024;
+}
+
+// The instantiation of a map the table lists for the pass (a map serves one
+// layer count), per cell.  `phase`: the phase-stamped build of map 5.
+using FwdKernel = void (*)(PdrnnLstmSmallFwdArgs);
+using BwdKernel = void (*)(PdrnnLstmSmallBwdArgs);
+template <int CELL>
+FwdKernel fwd_kernel(int map, bool phase) {
+  switch (map) {
+    case 0: return lstm_sw_fwd_kernel<1, 0, CELL>;
+    case 1: return lstm_sw_fwd_kernel<1, 1, CELL>;
+    case 2: return lstm_sw_fwd_kernel<2, 2, CELL>;
+    case 5:
+      if constexpr (CELL == 0) {
+        if (phase) return lstm_sw_fwd4_kernel<0, true>;
+      }
+      return lstm_sw_fwd4_kernel<CELL, false>;
+    case 6: return lstm_sw_fwd_kernel<2, 6, CELL>;
+    case 8: return lstm_sw_fwd8_kernel<CELL>;
+  }
+  return nullptr;
+}
+template <int CELL>
+BwdKernel bwd_kernel(int map) {
+  switch (map) {
+    case 0: return lstm_sw_bwd_kernel<1, 0, CELL>;
+    case 1: return lstm_sw_bwd_kernel<1, 1, CELL>;
+    case 2: return lstm_sw_bwd_kernel<2, 2, CELL>;
+    case 3: return lstm_sw_bwd_kernel<2, 3, CELL>;
+    case 4: return lstm_sw_bwd_kernel<2, 4, CELL>;
+  }
+  return nullptr;
+}
+
+hipError_t launch_fwd(const PdrnnLstmSmallFwdArgs* a, int map, hipStream_t st) {
+  if (!map_serves(map, false, a->NL) || !map_serves_T(map, a->NL, a->T)) return hipErrorInvalidValue;
+  const WaveMap& m = kMaps[map];
+  const size_t lds = fwd_lds(map, a->NL, a->T);
+  if (lds > 64 * 1024) return hipErrorInvalidConfiguration;
+  const bool phase = a->phase_stamps && a->stamps;
+  const FwdKernel k = a->cell == 1 ? fwd_kernel<1>(map, phase) : fwd_kernel<0>(map, phase);
+  hipLaunchKernelGGL(k, dim3((a->B + m.nb - 1) / m.nb), dim3(64 * m.waves), lds, st, *a);
   return hipGetLastError();
 }
-// Mode 8: 14,144 bytes of LDS plus the staged x rows (48 T).  Six workgroups
-// (three waves per SIMD) share a CU's 160 KiB only up to 26,624 bytes each
-// (2 KiB granules): T <= 256; longer sequences take mode 6.
-size_t fwd8_lds(int T) { return sizeof(float) * ((size_t)kF8X + (size_t)T * kXS); }
-hipError_t launch_fwd8(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  if (!pdrnn_lstm_sw_fwd8_ok(a->NL, a->T)) return hipErrorInvalidValue;  // (the planner falls back to mode 6)
-  if (a->cell == 1) hipLaunchKernelGGL(lstm_sw_fwd8_kernel<1>, dim3(a->B), dim3(128), fwd8_lds(a->T), st, *a);
-  else hipLaunchKernelGGL(lstm_sw_fwd8_kernel<0>, dim3(a->B), dim3(128), fwd8_lds(a->T), st, *a);
+hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, int map, hipStream_t st) {
+  if (!map_serves(map, true, a->NL) || !map_serves_T(map, a->NL, a->T)) return hipErrorInvalidValue;
+  const WaveMap& m = kMaps[map];
+  // register dW: one slab row per workgroup; reads the x rows and the h sequence
+  if (m.rdw && (!a->slab || !a->xg_out || a->xg_ld > 16 || !a->hseq)) return hipErrorInvalidValue;
+  const BwdKernel k = a->cell == 1 ? bwd_kernel<1>(map) : bwd_kernel<0>(map);
+  hipLaunchKernelGGL(k, dim3((a->B + m.nb - 1) / m.nb), dim3(64 * m.waves), bwd_lds(map, a->NL), st, *a);
   return hipGetLastError();
 }
-hipError_t launch_fwd4(const PdrnnLstmSmallFwdArgs* a, hipStream_t st) {
-  const size_t lds = sizeof(float) * (2 * 2 * kHB + (size_t)a->T * kXS);
-  if (a->phase_stamps && a->stamps && a->cell == 0)
-    hipLaunchKernelGGL((lstm_sw_fwd4_kernel<0, true>), dim3(a->B), dim3(256), lds, st, *a);
-  else if (a->cell == 1) hipLaunchKernelGGL(lstm_sw_fwd4_kernel<1>, dim3(a->B), dim3(256), lds, st, *a);
-  else hipLaunchKernelGGL(lstm_sw_fwd4_kernel<0>, dim3(a->B), dim3(256), lds, st, *a);
-  return hipGetLastError();
+
+// The lean training contract of the family: zero initial state, the loss
+// through the fused head on h_T, dL/dh_T of the top layer only.
+bool fwd_args_ok(const PdrnnLstmSmallFwdArgs& a) {
+  if (!pdrnn_lstm_sw_ok(kH, a.I, a.NL, a.cell) || a.h0 || a.c0) return false;
+  if (!a.act || !a.hseq || a.B <= 0 || a.T <= 0) return false;
+  if (!pdrnn_lstm_sw_fits(a.NL, a.B, a.T)) return false;  // 2 GiB descriptor range
+  if (a.head_w && (a.C > 16 || a.C < 1 || !a.labels || !a.slab || !a.dh_top)) return false;
+  return !a.xg_out || (a.xg_ld >= a.I && a.xg_ld <= kXS);
 }
-template <int NL, int MODE>
-hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, hipStream_t st) {
-  constexpr int NB = sw_nb(MODE);
-  const int grid = (a->B + NB - 1) / NB;
-  const int block = MODE == 4 ? 256 : MODE >= 2 ? 64 * NL : 64;
-  const size_t lds = bwd_lds(NL, NB, MODE >= 4 ? 8 : 2);
-  if (a->cell == 1) hipLaunchKernelGGL((lstm_sw_bwd_kernel<NL, MODE, 1>), dim3(grid), dim3(block), lds, st, *a);
-  else hipLaunchKernelGGL((lstm_sw_bwd_kernel<NL, MODE, 0>), dim3(grid), dim3(block), lds, st, *a);
-  return hipGetLastError();
+bool bwd_args_ok(const PdrnnLstmSmallBwdArgs& a) {
+  if (!pdrnn_lstm_sw_ok(kH, a.I, a.NL, a.cell)) return false;
+  if (a.h0 || a.c0 || a.dout || a.dcn || a.dx || a.dh0 || a.dc0 || !a.dhn || !a.dhn_top_only) return false;
+  return a.act && a.B > 0 && a.T > 0 && pdrnn_lstm_sw_fits(a.NL, a.B, a.T);  // 2 GiB descriptor range
 }
 
 }  // namespace
 }  // namespace pdrnn
 
 using namespace pdrnn;
-
-extern "C" int pdrnn_lstm_sw_fwd8_ok(int NL, int T) {
-  return (NL == 2 && T > 0 && T % kCT == 0 && 6 * ((fwd8_lds(T) + 2047) / 2048 * 2048) <= 160 * 1024) ? 1 : 0;
-}
-
 
 extern "C" int pdrnn_lstm_sw_ok(int H, int I, int NL, int cell) {
   return (H == kH && I >= 1 && I <= kXS && (NL == 1 || NL == 2) && (cell == 0 || cell == 1)) ? 1 : 0;
@@ -1660,107 +1699,72 @@ extern "C" int pdrnn_lstm_sw_fits(int NL, int B, int T) {
   return (NL >= 1 && B >= 1 && T >= 1 && rows * 5 * kH * 4 < ((int64_t)1 << 31)) ? 1 : 0;
 }
 
-// Measured (bench/sw_probe.cpp, profiles/r5/sw): two-layer stacks run one
-// wave per layer up to one wave per SIMD (mode 2) -- the forward two waves
-// per layer up to half a wave per SIMD (mode 5: 56.5 vs 62.0 us at B = 180,
-// 73.1 vs 81.8 at 512, slower above, profiles/r5/sw/fwd4_probe.log); above, the forward keeps
-// that map at three waves per SIMD with layer 1's input projection hoisted
-// onto the matrix cores per 16-step chunk (mode 8: the same bits as mode 6,
+// The plan: which map runs each pass of a batch.  Measured (bench/sw_probe.cpp,
+// profiles/r5/sw): two-layer stacks run one wave per layer up to one wave per
+// SIMD (map 2) -- the forward two waves per layer up to half a wave per SIMD
+// (map 5: 56.5 vs 62.0 us at B = 180, 73.1 vs 81.8 at 512, slower above,
+// profiles/r5/sw/fwd4_probe.log), where the backward forms the weight
+// gradients itself (map 4: no dW launch; 55.7 us against 54.7 + 16.9 at
+// B = 180, profiles/r5/sw/dw4_probe.log) and both fit one launch.  Above one
+// wave per SIMD the forward keeps the layer waves at three per SIMD with layer
+// 1's input projection on the matrix cores (map 8: the same bits as map 6,
 // the per-step map, and 1.0-1.5 % on the headline step at B = 1440 / 1152,
-// profiles/r7/fwd_chunked.md; mode 6 where pdrnn_lstm_sw_fwd8_ok refuses T)
-// and the backward takes two sequences per wave (mode 3).  Up to two workgroups per CU the backward
-// forms the weight gradients itself (mode 4: two more waves per workgroup on
-// the matrix cores, no dW launch; 55.7 us against 54.7 + 16.9 at B = 180,
-// profiles/r5/sw/dw4_probe.log; T % 4 == 0, the caller falls back to mode 2
-// otherwise).  One layer: one wave per sequence (mode 0),
-// two above one wave per SIMD (mode 1).  PDRNN_TUNE sw_mode / sw_bwd_mode
-// override (sw_mode alone: both passes).
-extern "C" int pdrnn_lstm_sw_mode(int NL, int B, int backward) {
-  int m = pdrnn_tune_int(backward ? "sw_bwd_mode" : "sw_mode", -1);
-  if (m < 0 && backward) m = pdrnn_tune_int("sw_mode", -1);
-  if (m >= 0) {
-    if (((m >= 0 && m <= 6) || m == 8) && (m < 2 || NL == 2) && (m != 6 || !backward) && (m != 4 || backward) &&
-        (m != 5 || !backward) && (m != 8 || !backward))
-      return m;
-  }
-  const int simds = 4 * sw_cus();
-  // (modes 4 / 5: four waves per workgroup, two workgroups per CU)
-  if (NL == 2 && 2 * B <= simds) return backward ? 4 : 5;
-  if (NL == 2) return B <= simds ? 2 : backward ? 3 : 8;  // (8: the caller falls back to 6 for the T it does not serve)
-  return B <= simds ? 0 : 1;
+// profiles/r7/fwd_chunked.md) and the backward takes two sequences per wave
+// (map 3).  One layer: one wave per sequence (map 0), two above one wave per
+// SIMD (map 1).  PDRNN_TUNE sw_mode / sw_bwd_mode override (sw_mode alone:
+// both passes); a map the table does not list for the pass and layer count is
+// ignored.  A map that does not run this T gives way last: 4 -> 2, 8 -> 6.
+extern "C" int pdrnn_lstm_sw_plan_cus(int NL, int B, int T, int cus, PdrnnLstmSwPlan* plan) {
+  if ((NL != 1 && NL != 2) || T <= 0 || cus <= 0 || !pdrnn_lstm_sw_fits(NL, B, T)) return 0;
+  const int simds = 4 * cus;
+  int f, b;
+  if (NL == 1) f = b = B <= simds ? 0 : 1;
+  else if (2 * B <= simds) f = 5, b = 4;  // (four waves per workgroup, two workgroups per CU)
+  else if (B <= simds) f = b = 2;
+  else f = 8, b = 3;
+  const int of = pdrnn_tune_int("sw_mode", -1);
+  int ob = pdrnn_tune_int("sw_bwd_mode", -1);
+  if (ob < 0) ob = of;
+  if (map_serves(of, false, NL)) f = of;
+  if (map_serves(ob, true, NL)) b = ob;
+  if (!map_serves_T(b, NL, T)) b = 2;  // register dW: whole 4-step K steps
+  if (!map_serves_T(f, NL, T)) f = 6;  // whole 16-step chunks, six workgroups per CU
+  plan->fwd_map = f;
+  plan->bwd_map = b;
+  plan->fwd_nb = kMaps[f].nb;
+  plan->bwd_nb = kMaps[b].nb;
+  plan->register_dw = kMaps[b].rdw ? 1 : 0;
+  plan->one_launch = (f == 5 && b == 4 && step_lds(T) <= 64 * 1024) ? 1 : 0;
+  return 1;
 }
-
-extern "C" int pdrnn_lstm_sw_nb(int mode) { return mode_nb(mode); }
-
-namespace {
-size_t step_lds(int T) { return std::max(sizeof(float) * (2 * 2 * kHB + (size_t)T * kXS), bwd_lds(2, 1, 8)); }
-}  // namespace
-
-extern "C" int pdrnn_lstm_sw_step_ok(int NL, int B, int T) {
-  if (NL != 2 || B <= 0 || T <= 0 || T % 4 || !pdrnn_lstm_sw_fits(NL, B, T)) return 0;
-  if (pdrnn_lstm_sw_mode(NL, B, 0) != 5 || pdrnn_lstm_sw_mode(NL, B, 1) != 4) return 0;
-  return step_lds(T) <= 64 * 1024 ? 1 : 0;
-}
-
-extern "C" hipError_t pdrnn_lstm_sw_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b,
-                                         hipStream_t st) {
-  if (!pdrnn_lstm_sw_ok(kH, f->I, f->NL, f->cell) || f->NL != 2 || f->h0 || f->c0 || b->cell != f->cell)
-    return hipErrorInvalidValue;
-  if (!f->act || !f->hseq || f->B <= 0 || f->T <= 0 || f->T % 4 || !pdrnn_lstm_sw_fits(f->NL, f->B, f->T))
-    return hipErrorInvalidValue;
-  if (!f->head_w || f->C > 16 || f->C < 1 || !f->labels || !f->slab || !f->dh_top) return hipErrorInvalidValue;
-  if (!f->xg_out || f->xg_ld < f->I || f->xg_ld > 16) return hipErrorInvalidValue;
-  if (b->B != f->B || b->T != f->T || b->NL != 2 || b->act != f->act || b->hseq != f->hseq || b->dhn != f->dh_top ||
-      !b->dhn_top_only || !b->slab || b->xg_out != f->xg_out || b->h0 || b->c0 || b->dout || b->dcn || b->dx ||
-      b->dh0 || b->dc0)
-    return hipErrorInvalidValue;
-  const size_t lds = step_lds(f->T);
-  if (lds > 64 * 1024) return hipErrorInvalidConfiguration;
-  if (f->cell == 1) hipLaunchKernelGGL(lstm_sw_step_kernel<1>, dim3(f->B), dim3(256), lds, st, *f, *b);
-  else hipLaunchKernelGGL(lstm_sw_step_kernel<0>, dim3(f->B), dim3(256), lds, st, *f, *b);
-  return hipGetLastError();
+extern "C" int pdrnn_lstm_sw_plan(int NL, int B, int T, PdrnnLstmSwPlan* plan) {
+  return pdrnn_lstm_sw_plan_cus(NL, B, T, sw_cus(), plan);
 }
 
 extern "C" hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t st) {
-  if (!pdrnn_lstm_sw_ok(kH, a->I, a->NL, a->cell) || a->h0 || a->c0) return hipErrorInvalidValue;
-  if (!a->act || !a->hseq || a->B <= 0 || a->T <= 0) return hipErrorInvalidValue;
-  if (!pdrnn_lstm_sw_fits(a->NL, a->B, a->T)) return hipErrorInvalidValue;  // 2 GiB descriptor range
-  if (a->head_w && (a->C > 16 || a->C < 1 || !a->labels || !a->slab || !a->dh_top)) return hipErrorInvalidValue;
-  if (a->xg_out && (a->xg_ld < a->I || a->xg_ld > kXS)) return hipErrorInvalidValue;
-  if (mode == 8) return launch_fwd8(a, st);
-  if (fwd_lds(a->NL, mode_nb(mode), a->T) > 64 * 1024) return hipErrorInvalidConfiguration;
-  if (a->NL == 1) {
-    if (mode == 0) return launch_fwd<1, 0>(a, st);
-    if (mode == 1) return launch_fwd<1, 1>(a, st);
-    return hipErrorInvalidValue;
-  }
-  if (mode == 0) return launch_fwd<2, 0>(a, st);
-  if (mode == 1) return launch_fwd<2, 1>(a, st);
-  if (mode == 2) return launch_fwd<2, 2>(a, st);
-  if (mode == 3) return launch_fwd<2, 3>(a, st);
-  if (mode == 6) return launch_fwd<2, 6>(a, st);
-  if (mode == 5) return launch_fwd4(a, st);
-  return hipErrorInvalidValue;
+  if (!fwd_args_ok(*a)) return hipErrorInvalidValue;
+  return launch_fwd(a, mode, st);
 }
 
 extern "C" hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t st) {
-  if (!pdrnn_lstm_sw_ok(kH, a->I, a->NL, a->cell)) return hipErrorInvalidValue;
-  if (a->h0 || a->c0 || a->dout || a->dcn || a->dx || a->dh0 || a->dc0 || !a->dhn || !a->dhn_top_only)
-    return hipErrorInvalidValue;  // lean contract only
-  if (!a->act || !a->dg_out || a->dg_st < 4 * kH || a->B <= 0 || a->T <= 0) return hipErrorInvalidValue;
-  if (!pdrnn_lstm_sw_fits(a->NL, a->B, a->T)) return hipErrorInvalidValue;  // 2 GiB descriptor range
-  if (a->NL == 1) {
-    if (mode == 0) return launch_bwd<1, 0>(a, st);
-    if (mode == 1) return launch_bwd<1, 1>(a, st);
+  if (!bwd_args_ok(*a) || !a->dg_out || a->dg_st < 4 * kH) return hipErrorInvalidValue;
+  return launch_bwd(a, mode, st);
+}
+
+// Maps 5 and 4 in one workgroup: the head and the staged x rows are not
+// optional, and both argument blocks describe the same batch and buffers.
+extern "C" hipError_t pdrnn_lstm_sw_step(const PdrnnLstmSmallFwdArgs* f, const PdrnnLstmSmallBwdArgs* b,
+                                         hipStream_t st) {
+  if (!fwd_args_ok(*f) || !bwd_args_ok(*b)) return hipErrorInvalidValue;
+  if (!map_serves(5, false, f->NL) || !map_serves_T(4, f->NL, f->T)) return hipErrorInvalidValue;
+  if (!f->head_w || !f->xg_out || !b->slab) return hipErrorInvalidValue;
+  if (b->cell != f->cell || b->B != f->B || b->T != f->T || b->NL != f->NL || b->act != f->act ||
+      b->hseq != f->hseq || b->dhn != f->dh_top || b->xg_out != f->xg_out)
     return hipErrorInvalidValue;
-  }
-  if (mode == 0) return launch_bwd<2, 0>(a, st);
-  if (mode == 1) return launch_bwd<2, 1>(a, st);
-  if (mode == 2) return launch_bwd<2, 2>(a, st);
-  if (mode == 3) return launch_bwd<2, 3>(a, st);
-  if (mode == 4) {  // register dW: one slab row per workgroup; reads the x rows and the h sequence
-    if (a->T % 4 || !a->slab || !a->xg_out || a->xg_ld > 16 || !a->hseq) return hipErrorInvalidValue;
-    return launch_bwd<2, 4>(a, st);
-  }
-  return hipErrorInvalidValue;
+  const size_t lds = step_lds(f->T);
+  if (lds > 64 * 1024) return hipErrorInvalidConfiguration;
+  const dim3 block(64 * kMaps[4].waves);
+  if (f->cell == 1) hipLaunchKernelGGL(lstm_sw_step_kernel<1>, dim3(f->B), block, lds, st, *f, *b);
+  else hipLaunchKernelGGL(lstm_sw_step_kernel<0>, dim3(f->B), block, lds, st, *f, *b);
+  return hipGetLastError();
 }

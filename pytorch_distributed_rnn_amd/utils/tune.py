@@ -6,7 +6,11 @@ same string: ``csrc/runtime/tune.cpp``).  Keys (README.md, tuning overrides):
 
 * small-H fused kernels: ``nb_fwd``, ``nb_bwd``, ``split_fwd``, ``split_bwd``,
   ``dwout`` (0 / force), ``dwout_nb``, ``prio``;
-* sequence-in-wave kernels: ``sw_mode``, ``sw_bwd_mode``;
+* sequence-in-wave kernels: ``sw_mode``, ``sw_bwd_mode`` -- a wave map id of
+  the table in ``csrc/kernels/lstm_sw.hip`` (forward 0, 1 on one layer and 2,
+  5, 6, 8 on two; backward 0, 1 and 2, 3, 4).  ``sw_mode`` alone applies to
+  both passes; an id the table does not list for the pass and layer count is
+  ignored (``lstm_sw_plan`` shows what runs);
 * large-H kernels: ``large_tile``, ``large_pp``, ``large_pp_bwd``, ``rows``,
   ``large_pipe``, ``large_chunks``, ``large_overlap``.
 
