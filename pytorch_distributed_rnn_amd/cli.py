@@ -9,13 +9,15 @@ so fabfile-style command lines keep working:
     mpirun -np 8 python main.py ... distributed          (rank from OMPI_* env)
     torchrun --nproc-per-node 8 main.py ... horovod
     main.py ... parameter-server --world-size 3 --rank 0
+    main.py --device cpu predict --checkpoint models/best-model.pt --split test
 
 Additions (all optional): ``--synthetic``, ``--cell {lstm,gru}``, ``--dtype
 {fp32,bf16,fp16}``, ``--bidirectional``, ``--trace`` / ``--profile DIR``,
 ``--backend``, ``--bucket-mb``, ``--cuda-graph``, ``--kernel {hip,torch}``, ``--resume``,
 ``--checkpoint-every``, ``--log-interval``, ``--weak-scaling``,
 ``--fault-delay-ms`` / ``--fault-rank`` (network fault injection stand-in for
-tc-netem), ``--history-file``.  Deviations from the reference, documented:
+tc-netem), ``--history-file``, and the ``predict`` subcommand (classify a split
+with a trained checkpoint; the model is rebuilt from the checkpoint itself).  Deviations from the reference, documented:
 ``--validation-fraction`` is honoured (the reference never passes it on),
 ``history.json`` is written by rank 0 only, ``--seed`` also seeds the
 train/validation split.
@@ -37,7 +39,10 @@ DEFAULT_ROOT = Path(os.environ.get("PDRNN_MOTION_DIR", Path(__file__).resolve().
 
 def build_parser(script_dir: Optional[Path] = None) -> argparse.ArgumentParser:
     root = Path(script_dir) if script_dir is not None else DEFAULT_ROOT
-    p = argparse.ArgumentParser(description="SusML JKTM")
+    # (no prefix matching of the global flags: the top-level parser looks at
+    # every word of the command line, and predict's --checkpoint would count as
+    # an ambiguous prefix of --checkpoint-directory / --checkpoint-every)
+    p = argparse.ArgumentParser(description="SusML JKTM", allow_abbrev=False)
     p.add_argument("--checkpoint-directory", default=root / "models", type=Path)
     p.add_argument("--dataset-path", default=root / "data", type=Path)
     p.add_argument("--output-path", default=None, type=Path)
@@ -100,6 +105,12 @@ def build_parser(script_dir: Optional[Path] = None) -> argparse.ArgumentParser:
     for name in ("local", "distributed", "horovod"):
         sp = sub.add_parser(name)
         sp.set_defaults(func=lambda args, _n=name: train(args, _n))
+    sp = sub.add_parser("predict", help="classify a split with a trained checkpoint")
+    sp.add_argument("--checkpoint", required=True, type=Path,
+                    help="a checkpoint written by training (best-model.pt, checkpoint-epoch-N.pt)")
+    sp.add_argument("--split", choices=("test", "validation", "train"), default="test")
+    sp.add_argument("--predictions-file", default="predictions.json", type=Path)
+    sp.set_defaults(func=predict)
     return p
 
 
@@ -196,9 +207,78 @@ def train(args, name: str):
     return trainer
 
 
+@torch.no_grad()
+def predict(args):
+    """``predict``: rebuild the model a checkpoint describes, classify one
+    split of the data set and write the predictions as JSON.  The split runs
+    as one batch, like the trainer's validation and test evaluation, so the
+    logged line is the one training printed for that model and split.  On the
+    GPU the batch is one launch of the fused inference kernel where it serves
+    the model (train/fused_eval.py), ``model.forward`` elsewhere."""
+    logging.getLogger().setLevel(args.log)
+    _apply_common(args)
+    from .data.loader import DeviceBatchLoader
+    from .data.motion import MotionDataset
+    from .models.motion import model_from_state_dict
+    from .ops.xent import CrossEntropyLoss
+    from .train import checkpoint as ckpt, fused_eval
+    from .train.formatter import TrainingMessageFormatter
+    from .train.trainer import default_device
+
+    state = ckpt.read_checkpoint(args.checkpoint)["model_state"]
+    cdt = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.dtype, torch.float32)
+    model = model_from_state_dict(state, compute_dtype=cdt)
+    for flag, given, have in (("--hidden-units", args.hidden_units, model.hidden_dim),
+                              ("--stacked-layer", args.stacked_layer, model.layer_dim),
+                              ("--cell", args.cell, model.cell),
+                              ("--bidirectional", args.bidirectional, model.bidirectional)):
+        # (only what the command line really says: the parser's defaults contradict nobody)
+        if given != have and any(a == flag or a.startswith(flag + "=") for a in getattr(args, "argv", ())):
+            logging.warning(f"{flag} {given} ignored: the checkpoint holds {have}")
+    dataset = dict(zip(MotionDataset.SPLITS, _load_datasets(args)))[args.split]
+    if dataset.num_features != model.lstm.input_size:
+        raise SystemExit(f"the checkpoint's model reads {model.lstm.input_size} features per step, "
+                         f"the data set has {dataset.num_features}")
+    device = torch.device("cpu") if args.device == "cpu" else default_device()
+    model = model.to(device).eval()
+    fused = None
+    if os.environ.get("PDRNN_FUSED_EVAL", "1") != "0" and fused_eval.supported(model, device):
+        fused = fused_eval.MotionEvalStep(model)
+    loader = DeviceBatchLoader(dataset, None, device=device, gather_in_kernel=device.type == "cuda",
+                               feature_dtype=cdt if device.type == "cuda" else None)
+    loss_fn = CrossEntropyLoss()
+    preds, loss_sum, correct = [], 0.0, 0
+    for batch in loader:
+        features, labels = batch[0], batch[1].long().reshape(-1)
+        idx = batch[2] if len(batch) == 3 else None
+        if fused is not None:
+            preds.append(fused(features, labels, idx)[1])
+        else:
+            logits = model(features, idx=idx) if idx is not None else model(features)
+            own = labels if idx is None else labels.index_select(0, idx)
+            pred = torch.argmax(logits, dim=1)
+            loss_sum += float(loss_fn(logits, own))
+            correct += int((pred == own).sum())
+            preds.append(pred)
+    if fused is not None:
+        loss_sum, _, correct, _ = fused.result()
+    predictions = torch.cat(preds).cpu().tolist()
+    examples = len(dataset)
+    loss = loss_sum / len(loader)
+    accuracy = float(correct) / examples
+    logging.info(f"Split {args.split} of size {examples}, checkpoint {args.checkpoint}")
+    logging.info(TrainingMessageFormatter(1).evaluation_message(accuracy, examples, None, loss, correct))
+    with open(args.predictions_file, "w") as f:
+        json.dump({"checkpoint": str(args.checkpoint), "split": args.split, "examples": examples, "loss": loss,
+                   "correct": correct, "accuracy": accuracy, "class_names": list(MotionDataset.LABELS),
+                   "predictions": predictions}, f)
+    return predictions
+
+
 def main(argv=None, script_dir: Optional[Path] = None):
     parser = build_parser(script_dir)
     args = parser.parse_args(argv)
+    args.argv = list(sys.argv[1:] if argv is None else argv)  # predict: which flags were given
     if args.seed is not None:
         torch.manual_seed(args.seed)
     torch.set_num_threads(max(1, args.num_threads))

@@ -365,6 +365,79 @@ std::vector<Tensor> lstm_sw_fwd(const Tensor& x, const std::vector<Tensor>& w, i
   return {hseq, act, hn, cn};
 }
 
+// Motion inference in one launch (pdrnn_lstm_sw_infer): the sequence-in-wave
+// forward built without the saved rows, the head writing logits, the argmax
+// and -- with labels -- one [loss / B, 1, correct] row per sequence.  x is the
+// [N, T, I] table, gathered through idx like the train step (labels likewise:
+// labels[idx[b]]).  mode < 0 asks the plan.  Returns (logits [B, C], pred [B],
+// seq_stats [B, 3] or None, hn, cn or None).
+py::tuple lstm_head_infer(const Tensor& x, const optional<Tensor>& idx, const optional<Tensor>& labels,
+                          const std::vector<Tensor>& w, const Tensor& head_w, const optional<Tensor>& head_b,
+                          int64_t H, int64_t NL, int64_t cell, bool round_bf16, int64_t mode, bool need_state) {
+  CHECK_HIP_TENSOR(x);
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "x must be float32 or bfloat16");
+  TORCH_CHECK(x.dim() == 3 && x.stride(2) == 1, "x must be [N, T, I] with contiguous rows");
+  const c10::DeviceGuard guard(x.device());
+  const int64_t I = x.size(2);
+  TORCH_CHECK(pdrnn_lstm_sw_ok((int)H, (int)I, (int)NL, (int)cell) == 1,
+              "motion inference serves H = 32, 1 <= I <= 12, 1 or 2 layers, LSTM (cell 0) or GRU (cell 1); got H=", H,
+              ", I=", I, ", layers=", NL, ", cell=", cell);
+  bool has_bias = false;
+  check_stack(w, NL, H, I, has_bias);
+  const bool gathered = idx.has_value() && idx->defined();
+  if (gathered)
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->is_contiguous() && idx->device() == x.device(),
+                "idx must be a contiguous int64 tensor on x's device");
+  TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H && head_w.is_contiguous() &&
+              head_w.scalar_type() == at::kFloat && head_w.device() == x.device(), "head weight must be fp32 [C, H]");
+  const int64_t C = head_w.size(0);
+  TORCH_CHECK(C >= 1 && C <= 16, "motion inference serves 1..16 classes, got ", C);
+  const bool has_hb = head_b.has_value() && head_b->defined();
+  if (has_hb)
+    TORCH_CHECK(head_b->numel() == C && head_b->is_contiguous() && head_b->scalar_type() == at::kFloat, "head bias [C]");
+  const bool has_lab = labels.has_value() && labels->defined();
+  if (has_lab)
+    TORCH_CHECK(labels->scalar_type() == at::kLong && labels->is_contiguous() && labels->device() == x.device() &&
+                labels->numel() >= x.size(0), "labels must be int64, one per row of x");
+
+  PdrnnLstmSmallFwdArgs a{};
+  set_input(a, x, idx, true);
+  set_weights(a, w, NL);
+  const int64_t B = a.B, T = a.T;
+  TORCH_CHECK(B > 0 && T > 0, "motion inference: empty batch");
+  int map = (int)mode;
+  if (mode < 0)
+    TORCH_CHECK(pdrnn_lstm_sw_infer_plan((int)NL, (int)B, (int)T, &map) > 0,
+                "motion inference: no wave map runs T=", T, " (the staged x rows exceed 64 KiB of LDS)");
+  auto opts = x.options().dtype(at::kFloat);
+  Tensor logits = at::empty({B, C}, opts), pred = at::empty({B}, opts.dtype(at::kLong));
+  Tensor seq_stats, hn, cn;
+  a.head_w = head_w.data_ptr<float>();
+  a.head_b = has_hb ? head_b->data_ptr<float>() : nullptr;
+  a.logits = logits.data_ptr<float>();
+  a.pred = pred.data_ptr<int64_t>();
+  if (has_lab) {
+    seq_stats = at::empty({B, 3}, opts);
+    a.labels = labels->data_ptr<int64_t>();
+    a.seq_stats = seq_stats.data_ptr<float>();
+  }
+  if (need_state) {
+    hn = at::empty({NL, B, H}, opts);
+    a.hn = hn.data_ptr<float>();
+    cn = at::empty({NL, B, H}, opts);  // (GRU: the last candidate n_T, as lstm_sw_fwd returns it)
+    a.cn = cn.data_ptr<float>();
+  }
+  a.inv_batch = 1.f / (float)B;
+  a.C = (int)C; a.NL = (int)NL; a.cell = (int)cell; a.w_bf16 = round_bf16 ? 1 : 0;
+  const hipError_t err = pdrnn_lstm_sw_infer(&a, map, cur_stream());
+  TORCH_CHECK(err != hipErrorInvalidValue && err != hipErrorInvalidConfiguration, "motion inference: wave map ", map,
+              " does not run layers=", NL, ", T=", T, " (a map of another layer count, T not a multiple of the "
+              "map's chunk, or more than 64 KiB of LDS)");
+  HIP_LAUNCH_CHECK(err);
+  auto opt_t = [](const Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+  return py::make_tuple(logits, pred, opt_t(seq_stats), opt_t(hn), opt_t(cn));
+}
+
 // Returns {dparams_flat[P] (nn.LSTM parameter order), dx, dh0, dc0}.
 std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx,
                                    const std::vector<optional<Tensor>>& w_in, const optional<Tensor>& h0,
@@ -1791,6 +1864,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_sw_fwd", &lstm_sw_fwd, "sequence-in-wave stack forward in one wave map -> (hseq, act, hn, cn)",
         py::arg("x"), py::arg("w"), py::arg("H"), py::arg("NL"), py::arg("mode"), py::arg("cell") = 0,
         py::arg("round_bf16") = false);
+  m.def("lstm_head_infer", &lstm_head_infer,
+        "motion inference in one launch -> (logits [B,C], pred [B], seq_stats [B,3] or None, hn, cn or None)",
+        py::arg("x"), py::arg("idx"), py::arg("labels"), py::arg("w"), py::arg("head_w"), py::arg("head_b"),
+        py::arg("H"), py::arg("NL"), py::arg("cell") = 0, py::arg("round_bf16") = false, py::arg("mode") = -1,
+        py::arg("need_state") = false);
+  m.def("lstm_sw_infer_plan", [](int64_t NL, int64_t B, int64_t T, const optional<int64_t>& cus) {
+    int map = -1;
+    const int nb = cus.has_value() ? pdrnn_lstm_sw_infer_plan_cus((int)NL, (int)B, (int)T, (int)*cus, &map)
+                                   : pdrnn_lstm_sw_infer_plan((int)NL, (int)B, (int)T, &map);
+    TORCH_CHECK(nb > 0, "no sequence-in-wave map runs inference for NL=", NL, " B=", B, " T=", T);
+    py::dict d;
+    d["map"] = map; d["nb"] = nb;
+    return d;
+  }, "the wave map of lstm_head_infer for B sequences of T steps and its sequences per workgroup: the forward "
+     "thresholds of lstm_sw_plan without its batch limit.  cus: for a device of that many compute units",
+        py::arg("NL"), py::arg("B"), py::arg("T"), py::arg("cus") = py::none());
   m.def("lstm_small_supported", [](int64_t H, int64_t I, int64_t NL) {
     return pdrnn_lstm_small_supported((int)H, (int)I, (int)NL) != 0;
   });

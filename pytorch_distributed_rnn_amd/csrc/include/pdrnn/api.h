@@ -63,6 +63,12 @@ typedef struct {
   // sequence-in-wave map 5 with stamps: the phase-stamped build (stamps rows
   // of 24: the loop stamps, then per-step cycle sums of waves 0 / 2)
   int phase_stamps;
+  // sequence-in-wave inference (pdrnn_lstm_sw_infer): the head's outputs.
+  // seq_stats row b = [(lse - z_y) * inv_batch, 1, correct], written only
+  // when labels is set.  NULL everywhere else.
+  float* logits;             // [B, C]
+  int64_t* pred;             // [B] argmax of the logits, the lowest index on ties
+  float* seq_stats;          // [B, 3] or NULL
 } PdrnnLstmSmallFwdArgs;
 
 typedef struct {
@@ -195,6 +201,20 @@ int pdrnn_lstm_sw_plan_cus(int NL, int B, int T, int cus, PdrnnLstmSwPlan* plan)
 // layer count, or that does not run this T
 hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t stream);
 hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t stream);
+// Inference: the same forward maps built without the saved rows (no act /
+// hseq / xg_out stores in the step loop; h_n / c_n are the training forward's
+// bits) and with the head writing logits / pred / seq_stats instead of
+// gradients.  The plan applies the forward thresholds of pdrnn_lstm_sw_plan_cus
+// and PDRNN_TUNE sw_mode, not pdrnn_lstm_sw_fits: no activation rows, so the
+// only size limit is the map's LDS (<= 64 KiB; map 1 gives way to map 0 where
+// two sequences' x rows exceed it).  Returns the map's sequences
+// per workgroup (grid = ceil(B / nb)), 0 where no map runs the shape.
+// pdrnn_lstm_sw_infer: hipErrorInvalidValue when a training-only
+// field is set (act, hseq, xg_out, slab, dh_top, h0, c0) or head_w / logits /
+// pred is missing.
+int pdrnn_lstm_sw_infer_plan(int NL, int B, int T, int* map);
+int pdrnn_lstm_sw_infer_plan_cus(int NL, int B, int T, int cus, int* map);
+hipError_t pdrnn_lstm_sw_infer(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t stream);
 
 // Column sums of a [rows, P] fp32 slab into out[P] (out = beta*out + sum).
 // Two deterministic passes through `work` ([split, P] floats, split <= 64)

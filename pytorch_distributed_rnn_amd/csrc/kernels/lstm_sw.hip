@@ -37,6 +37,10 @@
 //    below holds one row per map id, and every kernel constant, launch
 //    geometry and planner rule reads it.  pdrnn_lstm_sw_plan picks the maps
 //    of a batch (docs/DESIGN.md §2b).
+//  * Every forward body also has an inference build (INFER): the same step
+//    with nothing saved, no global store in the step loop, and a head that
+//    writes logits / predictions / per-sequence statistics
+//    (pdrnn_lstm_sw_infer, pdrnn_lstm_sw_infer_plan).
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"
 #include "pdrnn/motion_head.h"
@@ -305,7 +309,8 @@ PDRNN_DEVICE constexpr int fwd_lds_floats_hb() { return NB * NL * 2 * kHB; }
 // at once (element-wise loads, one dependent round per 4 elements per thread,
 // cost the single-layer forward 16 us of ~100 at B = 1440, 23 with bf16 x,
 // profiles/r6/x_staging.md).  Returns false when the layout does not allow it.
-template <int NB>
+// INFER: the inference builds, no xg_out copy.
+template <int NB, bool INFER = false>
 PDRNN_DEVICE bool stage_x_vec(const PdrnnLstmSmallFwdArgs& a, float* xs, const int (&bsrc)[NB], const int (&bidx)[NB],
                               const int (&vint)[NB], int tid, int nthr) {
   const int T = a.T, I = a.I;
@@ -337,7 +342,8 @@ PDRNN_DEVICE bool stage_x_vec(const PdrnnLstmSmallFwdArgs& a, float* xs, const i
         const int e0 = q * cpe;
         int t = e0 / I, k = e0 - t * I;  // (one division per chunk, then stepped)
         float* xrow = xs + (n * T + t) * kXS;
-        float* grow = a.xg_out ? a.xg_out + ((int64_t)pick<NB>(bidx, n) * T + t) * xg_ld : nullptr;
+        float* grow = nullptr;  // (stays null in the inference builds: the copies below fold away)
+        if constexpr (!INFER) grow = a.xg_out ? a.xg_out + ((int64_t)pick<NB>(bidx, n) * T + t) * xg_ld : nullptr;
         const bool gv = grow != nullptr && pick<NB>(vint, n);
         for (int j = 0; j < cpe; ++j) {
           const float val = esz == 2 ? __uint_as_float((j & 1 ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu) << 16)
@@ -353,7 +359,7 @@ PDRNN_DEVICE bool stage_x_vec(const PdrnnLstmSmallFwdArgs& a, float* xs, const i
       }
     }
   }
-  if (a.xg_out && xg_ld > I) {  // the dW kernel reads xg_ld columns: zero pads
+  if (!INFER && a.xg_out && xg_ld > I) {  // the dW kernel reads xg_ld columns: zero pads
     const int padw = xg_ld - I;
     for (int e = tid; e < NB * T * padw; e += nthr) {
       const int n = e / (T * padw), rem = e - n * (T * padw);
@@ -367,7 +373,11 @@ PDRNN_DEVICE bool stage_x_vec(const PdrnnLstmSmallFwdArgs& a, float* xs, const i
 // Maps 0 / 1 (one layer) and 2 / 6 (two layers, a wave per layer).  Map 6
 // holds <= 168 VGPRs: three waves per SIMD, so B = 1440 (2880 layer waves on
 // 1024 SIMDs) is one residency round with every SIMD loaded evenly.
-template <int NL, int MODE, int CELL = 0>
+// INFER (here and in fwd4_body / lstm_sw_fwd8_kernel): the inference build.
+// The step is the same source, so h_n / c_n are the training build's bits,
+// but nothing is saved -- no act / hseq rows, no xg_out copy, no global store
+// in the step loop -- and the epilogue's head is motion_head_infer.
+template <int NL, int MODE, int CELL = 0, bool INFER = false>
 __global__ void __launch_bounds__(64 * kMaps[MODE].waves) __attribute__((amdgpu_waves_per_eu(kMaps[MODE].eu_cap)))
 lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   constexpr int NB = kMaps[MODE].nb;
@@ -406,7 +416,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   const bool xvec = NB == 2 && a.x_st == I && a.x_sb == (int64_t)T * I;
   for (int e = tid; e < fwd_lds_floats_hb<NL, NB>() + (xvec ? NB * T * kXS : 0); e += nthr) hb[e] = 0.f;
   if (xvec) lds_barrier();
-  if (!(xvec && stage_x_vec<NB>(a, xs, bsrc, bidx, vint, tid, nthr))) {
+  if (!(xvec && stage_x_vec<NB, INFER>(a, xs, bsrc, bidx, vint, tid, nthr))) {
     const int per = T * kXS, tot = NB * per;
     const int xg_ld = a.xg_ld;
     for (int e0 = tid; e0 < tot; e0 += 4 * nthr) {
@@ -426,7 +436,7 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
           const int n = e / per, rem = e - n * per;
           const int t = rem / kXS, k = rem - t * kXS;
           xs[e] = v[r];
-          if (a.xg_out && k < xg_ld && pick<NB>(vint, n))
+          if (!INFER && a.xg_out && k < xg_ld && pick<NB>(vint, n))
             a.xg_out[((int64_t)pick<NB>(bidx, n) * T + t) * xg_ld + k] = v[r];
         }
       }
@@ -436,6 +446,9 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   // not drain here -- a __syncthreads() would wait for them (~1-3 us)
   lds_barrier();
 
+  // (the saved rows' descriptors, lane offsets, masks and row(): used by
+  // store_cell alone, so the inference builds, where a.act / a.hseq are null
+  // and store_cell is compiled out, form none of them)
   const __amdgpu_buffer_rsrc_t r_act = uniform_rsrc(a.act);
   const __amdgpu_buffer_rsrc_t r_h = uniform_rsrc(a.hseq);
   const uint32_t s_ = odd ? 1u : 0u;
@@ -486,8 +499,10 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
     cst[l][n] = act ? r.c : cst[l][n];
     hst[l][n] = act ? r.h : hst[l][n];
     hbuf(n, l, t & 1)[u] = hst[l][n];
-    const uint32_t rw = row(l, n, min(max(t, 0), T - 1));
-    store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, act ? vmask[n] : kOOR, rw);
+    if constexpr (!INFER) {
+      const uint32_t rw = row(l, n, min(max(t, 0), T - 1));
+      store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, act ? vmask[n] : kOOR, rw);
+    }
   };
   const pdrnn_f2 gk = odd ? pdrnn_f2{1.f, 0.f} : pdrnn_f2{2.f, -1.f};
   auto cmp0 = [&](const FwdW<6>& W, int t, const float4 (&v)[NB][6]) {
@@ -559,7 +574,8 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
   if constexpr (NB > 1) {
     if (a.head_w && top_wave) {
 #pragma unroll
-      for (int n = 0; n < NB; ++n) hin[n] = head_load(a, pick<NB>(bidx, n), u);
+      for (int n = 0; n < NB; ++n)
+        hin[n] = INFER ? head_load_infer(a, pick<NB>(bidx, n), u) : head_load(a, pick<NB>(bidx, n), u);
     }
   }
 #pragma unroll
@@ -573,8 +589,13 @@ lstm_sw_fwd_kernel(PdrnnLstmSmallFwdArgs a) {
       if (!odd && a.cn) a.cn[((int64_t)l * B + b) * kH + u] = cst[l][n];
     }
     if (a.head_w && top_wave) {
-      if constexpr (NB > 1) motion_head(a, b, hst[NL - 1][n], u, odd, hin[n]);
-      else motion_head(a, b, hst[NL - 1][n], u, odd);
+      if constexpr (INFER) {
+        if constexpr (NB > 1) motion_head_infer(a, b, hst[NL - 1][n], u, odd, hin[n]);
+        else motion_head_infer(a, b, hst[NL - 1][n], u, odd);
+      } else {
+        if constexpr (NB > 1) motion_head(a, b, hst[NL - 1][n], u, odd, hin[n]);
+        else motion_head(a, b, hst[NL - 1][n], u, odd);
+      }
     }
   }
   if (a.stamps && tid == 0) stamp_exit(a.stamps + (uint64_t)blockIdx.x * 8, sr_in);
@@ -654,7 +675,7 @@ PDRNN_DEVICE Fwd4W<NC> load_fwd4_w(const PdrnnLstmSmallFwdArgs& a, int l, int u,
 // operand reads landed, after the products, after the quad reduce, after the
 // cell and its stores; per-phase cycle sums over steps [16, T - 16) of waves 0
 // (layer 0) and 2 (layer 1), written behind the loop stamps (row of 24).
-template <int CELL = 0, bool PH = false>
+template <int CELL = 0, bool PH = false, bool INFER = false>
 PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
@@ -676,13 +697,13 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
   for (int e = tid; e < 2 * 2 * kHB + (xvec ? T * kXS : 0); e += 256) hb[e] = 0.f;
   if (xvec) lds_barrier();
   const int bsrc1[1] = {bsrc}, bidx1[1] = {b}, vint1[1] = {1};
-  if (!(xvec && stage_x_vec<1>(a, xs, bsrc1, bidx1, vint1, tid, 256))) {
+  if (!(xvec && stage_x_vec<1, INFER>(a, xs, bsrc1, bidx1, vint1, tid, 256))) {
     for (int e = tid; e < T * kXS; e += 256) {
       const int t = e / kXS, k = e - t * kXS;
       const float x = ldx(a.x, (int64_t)bsrc * a.x_sb + (int64_t)t * a.x_st + min(k, I - 1), a.x_bf16);
       const float v = k < I ? x : 0.f;
       xs[e] = v;
-      if (a.xg_out && k < a.xg_ld) a.xg_out[((int64_t)b * T + t) * a.xg_ld + k] = v;
+      if (!INFER && a.xg_out && k < a.xg_ld) a.xg_out[((int64_t)b * T + t) * a.xg_ld + k] = v;
     }
   }
   lds_barrier();  // (as in lstm_sw_fwd_kernel; the one-launch step's __syncthreads drains them before its BPTT)
@@ -724,11 +745,13 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
     cst = act ? cn : cst;
     hst = act ? hn : hst;
     if (q == 0) hbuf(l, t & 1)[u] = hst;
-    const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((l * B + b) * T + min(max(t, 0), T - 1)));
-    const uint32_t m = act ? 0u : kOOR;
-    bstore(av, r_act, vo_a | m, rw * (5 * kH * 4));
-    bstore(cn, r_act, vo_c | m | lead, rw * (5 * kH * 4));
-    bstore(hn, r_h, vo_h | m | lead, rw * (kH * 4));
+    if constexpr (!INFER) {
+      const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((l * B + b) * T + min(max(t, 0), T - 1)));
+      const uint32_t m = act ? 0u : kOOR;
+      bstore(av, r_act, vo_a | m, rw * (5 * kH * 4));
+      bstore(cn, r_act, vo_c | m | lead, rw * (5 * kH * 4));
+      bstore(hn, r_h, vo_h | m | lead, rw * (kH * 4));
+    }
   };
   // phase stamps (PH only; compiled out otherwise)
   uint64_t ph_t[5] = {0, 0, 0, 0, 0}, ph_sum[5] = {0, 0, 0, 0, 0}, ph_prev = 0, ph_n = 0;
@@ -855,13 +878,18 @@ PDRNN_DEVICE void fwd4_body(const PdrnnLstmSmallFwdArgs& a) {
     // layer 1's last step t = T-1 went to slot (T-1) & 1)
     if (wv == 2) {
       const int hu = lane >> 1;
-      motion_head(a, b, hbuf(1, (T - 1) & 1)[hu], hu, (lane & 1) != 0);
+      if constexpr (INFER) motion_head_infer(a, b, hbuf(1, (T - 1) & 1)[hu], hu, (lane & 1) != 0);
+      else motion_head(a, b, hbuf(1, (T - 1) & 1)[hu], hu, (lane & 1) != 0);
     }
   }
   if (a.stamps && tid == 0) a.stamps[(uint64_t)blockIdx.x * (PH ? 24 : 8) + 5] = stamp_real();
 }
 template <int CELL, bool PH = false>
 __global__ void __launch_bounds__(64 * kMaps[5].waves) lstm_sw_fwd4_kernel(PdrnnLstmSmallFwdArgs a) { fwd4_body<CELL, PH>(a); }
+template <int CELL>
+__global__ void __launch_bounds__(64 * kMaps[5].waves) lstm_sw_fwd4_infer_kernel(PdrnnLstmSmallFwdArgs a) {
+  fwd4_body<CELL, false, true>(a);
+}
 
 // ---------------------------------------------------------------------------
 // Forward, layer 1's input projection hoisted onto the matrix cores (map 8,
@@ -895,6 +923,7 @@ __global__ void __launch_bounds__(64 * kMaps[5].waves) lstm_sw_fwd4_kernel(Pdrnn
 // ---------------------------------------------------------------------------
 constexpr int kCT = 16;          // steps per chunk (MFMA M)
 constexpr int kPS = 4 * kH + 4;  // P row stride, floats
+constexpr int kF8Res = 4;        // inference: W_ih^1 column tiles (of 8) resident in VGPRs
 // LDS floats of a workgroup: P[kCT][kPS] | h^0 ring [2][kCT][kHB] | h slots
 // [2 layers][2 parities][kHB] | layer 1's MFMA C seeds [4H] | x rows [T][kXS]
 constexpr int kF8Ring = kCT * kPS, kF8Slot = kF8Ring + 2 * kCT * kHB, kF8Bias = kF8Slot + 2 * 2 * kHB;
@@ -905,8 +934,15 @@ PDRNN_DEVICE float gate_scale(int q) { return kA * ((CELL == 0 ? q == 2 : q >= 2
 // gate row of P column p (see above)
 PDRNN_DEVICE int p_row(int p) { return (((p >> 1) & 1) + 2 * (p & 1)) * kH + (p >> 2); }
 
+// One MFMA B fragment element of W_ih^1: gate row r (scaled by sc), chain e
+// (even / odd columns), K step j -> column 8 j + 2 kk + e.  The one place the
+// resident tiles and the inference build's per-chunk tiles get their values.
+PDRNN_DEVICE float bw_frag(const PdrnnLstmSmallFwdArgs& a, int r, float sc, int kk, int e, int j) {
+  return wround(a.w_ih[1][(int64_t)r * kH + 8 * j + 2 * kk + e], a.w_bf16) * sc;
+}
+
 static_assert(kMaps[8].t_mult == kCT && kMaps[8].waves == 2, "map 8: whole chunks, a wave per layer");
-template <int CELL>
+template <int CELL, bool INFER = false>
 __global__ void __launch_bounds__(64 * kMaps[8].waves) __attribute__((amdgpu_waves_per_eu(kMaps[8].eu_cap)))
 lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -954,7 +990,7 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
         if (e < tot) {
           const int t = e / kXS, k = e - t * kXS;
           xs[e] = v[r];
-          if (a.xg_out && k < xg_ld) a.xg_out[((int64_t)b * T + t) * xg_ld + k] = v[r];
+          if (!INFER && a.xg_out && k < xg_ld) a.xg_out[((int64_t)b * T + t) * xg_ld + k] = v[r];
         }
       }
     }
@@ -975,8 +1011,10 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
     cst = r.c;
     hst = r.h;
     hs[(t & 1) * kHB + u] = r.h;
-    const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((wv * B + b) * T + t));
-    store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, 0u, rw);
+    if constexpr (!INFER) {
+      const uint32_t rw = __builtin_amdgcn_readfirstlane((uint32_t)((wv * B + b) * T + t));
+      store_cell(r, r_act, r_h, vo_a0, vo_a1, vo_c, vo_h, 0u, rw);
+    }
   };
 
   if (wv == 0) {
@@ -1008,7 +1046,11 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
     pdrnn_f2 wr[2][16];
     float seed[2];
     // B fragments of W_ih^1: column tile nt, chain e (even / odd columns), K step j -> column 8 j + 2 kk + e
-    float bw[8][2][4];
+    // (the inference build keeps kF8Res tiles and fetches the others from
+    // memory in every chunk, the same values (bw_frag): with all eight
+    // resident it spills, as the training build does)
+    constexpr int NR = INFER ? kF8Res : 8;
+    float bw[NR][2][4];
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int q = s + 2 * jj, r = q * kH + u;
@@ -1024,14 +1066,13 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
       seed[jj] = odd ? bsum : 0.f;
     }
 #pragma unroll
-    for (int nt = 0; nt < 8; ++nt) {
+    for (int nt = 0; nt < NR; ++nt) {
       const int r = p_row(16 * nt + mi);
       const float sc = gate_scale<CELL>(r / kH);
 #pragma unroll
       for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bw[nt][e][j] = wround(a.w_ih[1][(int64_t)r * kH + 8 * j + 2 * kk + e], a.w_bf16) * sc;
+        for (int j = 0; j < 4; ++j) bw[nt][e][j] = bw_frag(a, r, sc, kk, e, j);
     }
     for (int c = 0; c <= nch; ++c) {
       if (c > 0) {
@@ -1045,10 +1086,20 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
           for (int nt = 0; nt < 8; ++nt) {
             const float b0 = cseed[16 * nt + mi];
             f32x4 ce = {b0, b0, b0, b0}, co = {0.f, 0.f, 0.f, 0.f};
+            float bf[2][4];
+            if (nt >= NR) {  // (inference: this tile is not resident)
+              const int r = p_row(16 * nt + mi);
+              const float sc = gate_scale<CELL>(r / kH);
+#pragma unroll
+              for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bf[e][j] = bw_frag(a, r, sc, kk, e, j);
+            }
+            const float (&bt)[2][4] = nt < NR ? bw[nt] : bf;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              ce = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].x, bw[nt][0][j], ce, 0, 0, 0);
-              co = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].y, bw[nt][1][j], co, 0, 0, 0);
+              ce = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].x, bt[0][j], ce, 0, 0, 0);
+              co = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j].y, bt[1][j], co, 0, 0, 0);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) P[(4 * kk + r) * kPS + 16 * nt + mi] = ce[r] + co[r];
@@ -1085,7 +1136,10 @@ lstm_sw_fwd8_kernel(PdrnnLstmSmallFwdArgs a) {
   // ---- epilogue: h_n / c_n, then the fused head on the top layer's h_T ----
   if (!odd && a.hn) a.hn[((int64_t)wv * B + b) * kH + u] = hst;
   if (!odd && a.cn) a.cn[((int64_t)wv * B + b) * kH + u] = cst;
-  if (a.head_w && wv == 1) motion_head(a, b, hst, u, odd);
+  if (a.head_w && wv == 1) {
+    if constexpr (INFER) motion_head_infer(a, b, hst, u, odd);
+    else motion_head(a, b, hst, u, odd);
+  }
   if (a.stamps && tid == 0) stamp_exit(a.stamps + (uint64_t)blockIdx.x * 8, sr_in);
 }
 
@@ -1633,6 +1687,18 @@ FwdKernel fwd_kernel(int map, bool phase) {
   return nullptr;
 }
 template <int CELL>
+FwdKernel infer_kernel(int map) {
+  switch (map) {
+    case 0: return lstm_sw_fwd_kernel<1, 0, CELL, true>;
+    case 1: return lstm_sw_fwd_kernel<1, 1, CELL, true>;
+    case 2: return lstm_sw_fwd_kernel<2, 2, CELL, true>;
+    case 5: return lstm_sw_fwd4_infer_kernel<CELL>;
+    case 6: return lstm_sw_fwd_kernel<2, 6, CELL, true>;
+    case 8: return lstm_sw_fwd8_kernel<CELL, true>;
+  }
+  return nullptr;
+}
+template <int CELL>
 BwdKernel bwd_kernel(int map) {
   switch (map) {
     case 0: return lstm_sw_bwd_kernel<1, 0, CELL>;
@@ -1654,6 +1720,15 @@ hipError_t launch_fwd(const PdrnnLstmSmallFwdArgs* a, int map, hipStream_t st) {
   hipLaunchKernelGGL(k, dim3((a->B + m.nb - 1) / m.nb), dim3(64 * m.waves), lds, st, *a);
   return hipGetLastError();
 }
+hipError_t launch_infer(const PdrnnLstmSmallFwdArgs* a, int map, hipStream_t st) {
+  if (!map_serves(map, false, a->NL) || !map_serves_T(map, a->NL, a->T)) return hipErrorInvalidValue;
+  const WaveMap& m = kMaps[map];
+  const size_t lds = fwd_lds(map, a->NL, a->T);
+  if (lds > 64 * 1024) return hipErrorInvalidConfiguration;
+  const FwdKernel k = a->cell == 1 ? infer_kernel<1>(map) : infer_kernel<0>(map);
+  hipLaunchKernelGGL(k, dim3((a->B + m.nb - 1) / m.nb), dim3(64 * m.waves), lds, st, *a);
+  return hipGetLastError();
+}
 hipError_t launch_bwd(const PdrnnLstmSmallBwdArgs* a, int map, hipStream_t st) {
   if (!map_serves(map, true, a->NL) || !map_serves_T(map, a->NL, a->T)) return hipErrorInvalidValue;
   const WaveMap& m = kMaps[map];
@@ -1672,6 +1747,14 @@ bool fwd_args_ok(const PdrnnLstmSmallFwdArgs& a) {
   if (!pdrnn_lstm_sw_fits(a.NL, a.B, a.T)) return false;  // 2 GiB descriptor range
   if (a.head_w && (a.C > 16 || a.C < 1 || !a.labels || !a.slab || !a.dh_top)) return false;
   return !a.xg_out || (a.xg_ld >= a.I && a.xg_ld <= kXS);
+}
+// Inference: no saved rows, no gradients, no initial state; the head is not
+// optional (logits and pred are what the launch is for).
+bool infer_args_ok(const PdrnnLstmSmallFwdArgs& a) {
+  if (!pdrnn_lstm_sw_ok(kH, a.I, a.NL, a.cell) || a.B <= 0 || a.T <= 0) return false;
+  if (a.act || a.hseq || a.xg_out || a.slab || a.dh_top || a.h0 || a.c0) return false;
+  if (!a.head_w || a.C > 16 || a.C < 1 || !a.logits || !a.pred) return false;
+  return !a.seq_stats || a.labels;
 }
 bool bwd_args_ok(const PdrnnLstmSmallBwdArgs& a) {
   if (!pdrnn_lstm_sw_ok(kH, a.I, a.NL, a.cell)) return false;
@@ -1714,21 +1797,33 @@ extern "C" int pdrnn_lstm_sw_fits(int NL, int B, int T) {
 // SIMD (map 1).  PDRNN_TUNE sw_mode / sw_bwd_mode override (sw_mode alone:
 // both passes); a map the table does not list for the pass and layer count is
 // ignored.  A map that does not run this T gives way last: 4 -> 2, 8 -> 6.
-extern "C" int pdrnn_lstm_sw_plan_cus(int NL, int B, int T, int cus, PdrnnLstmSwPlan* plan) {
-  if ((NL != 1 && NL != 2) || T <= 0 || cus <= 0 || !pdrnn_lstm_sw_fits(NL, B, T)) return 0;
+namespace {
+// The maps by batch size, before the overrides and the rules on T.
+void plan_by_batch(int NL, int B, int cus, int& f, int& b) {
   const int simds = 4 * cus;
-  int f, b;
   if (NL == 1) f = b = B <= simds ? 0 : 1;
   else if (2 * B <= simds) f = 5, b = 4;  // (four waves per workgroup, two workgroups per CU)
   else if (B <= simds) f = b = 2;
   else f = 8, b = 3;
+}
+// The forward map after PDRNN_TUNE sw_mode and the map's rule on T
+int plan_fwd_map(int NL, int T, int f) {
   const int of = pdrnn_tune_int("sw_mode", -1);
-  int ob = pdrnn_tune_int("sw_bwd_mode", -1);
-  if (ob < 0) ob = of;
   if (map_serves(of, false, NL)) f = of;
+  if (!map_serves_T(f, NL, T)) f = 6;  // whole 16-step chunks, six workgroups per CU
+  return f;
+}
+}  // namespace
+
+extern "C" int pdrnn_lstm_sw_plan_cus(int NL, int B, int T, int cus, PdrnnLstmSwPlan* plan) {
+  if ((NL != 1 && NL != 2) || T <= 0 || cus <= 0 || !pdrnn_lstm_sw_fits(NL, B, T)) return 0;
+  int f, b;
+  plan_by_batch(NL, B, cus, f, b);
+  int ob = pdrnn_tune_int("sw_bwd_mode", -1);
+  if (ob < 0) ob = pdrnn_tune_int("sw_mode", -1);
   if (map_serves(ob, true, NL)) b = ob;
   if (!map_serves_T(b, NL, T)) b = 2;  // register dW: whole 4-step K steps
-  if (!map_serves_T(f, NL, T)) f = 6;  // whole 16-step chunks, six workgroups per CU
+  f = plan_fwd_map(NL, T, f);
   plan->fwd_map = f;
   plan->bwd_map = b;
   plan->fwd_nb = kMaps[f].nb;
@@ -1744,6 +1839,27 @@ extern "C" int pdrnn_lstm_sw_plan(int NL, int B, int T, PdrnnLstmSwPlan* plan) {
 extern "C" hipError_t pdrnn_lstm_sw_fwd(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t st) {
   if (!fwd_args_ok(*a)) return hipErrorInvalidValue;
   return launch_fwd(a, mode, st);
+}
+
+// The forward half of the plan above (whether the store-free builds would
+// rather switch maps elsewhere has not been measured), without the activation
+// rows' limit pdrnn_lstm_sw_fits.
+extern "C" int pdrnn_lstm_sw_infer_plan_cus(int NL, int B, int T, int cus, int* map) {
+  if ((NL != 1 && NL != 2) || B <= 0 || T <= 0 || cus <= 0) return 0;
+  int f, b;
+  plan_by_batch(NL, B, cus, f, b);
+  f = plan_fwd_map(NL, T, f);
+  if (f == 1 && fwd_lds(1, NL, T) > 64 * 1024) f = 0;  // two sequences' x rows do not fit: one per wave
+  if (fwd_lds(f, NL, T) > 64 * 1024) return 0;
+  *map = f;
+  return kMaps[f].nb;
+}
+extern "C" int pdrnn_lstm_sw_infer_plan(int NL, int B, int T, int* map) {
+  return pdrnn_lstm_sw_infer_plan_cus(NL, B, T, sw_cus(), map);
+}
+extern "C" hipError_t pdrnn_lstm_sw_infer(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t st) {
+  if (!infer_args_ok(*a)) return hipErrorInvalidValue;
+  return launch_infer(a, mode, st);
 }
 
 extern "C" hipError_t pdrnn_lstm_sw_bwd(const PdrnnLstmSmallBwdArgs* a, int mode, hipStream_t st) {

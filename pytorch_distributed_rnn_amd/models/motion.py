@@ -14,7 +14,7 @@ neither the forward nor the backward materialises the [B, T, H] output stream
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Dict, Optional
 
 import torch
 from torch import Tensor, nn
@@ -61,6 +61,23 @@ class MotionModel(nn.Module):
             _, hn = self.lstm(x)
         return self._head(hn[-1])
 
+    @torch.no_grad()
+    def predict(self, x: Tensor, idx: Optional[Tensor] = None) -> Tensor:
+        """Logits of ``x`` (or of rows ``idx`` of the table ``x``) without
+        gradients and without dropout: one launch of the fused inference
+        kernel where it serves the model (train/fused_eval.py), else
+        ``forward`` in evaluation mode."""
+        from ..train import fused_eval
+        step = fused_eval.step_for(self) if x.is_cuda else None
+        if step is not None:
+            return step(x, None, idx)[0]
+        was_training = self.training
+        self.eval()
+        try:
+            return self.forward(x, idx=idx)
+        finally:
+            self.train(was_training)
+
     def _head(self, h: Tensor) -> Tensor:
         """The linear head; on the GPU on the in-tree narrow fp32 GEMM
         (ops/gemm.linear: forward, dX, dW with db as its row sums)."""
@@ -68,3 +85,29 @@ class MotionModel(nn.Module):
         if h.is_cuda:
             return linear(h, self.fc.weight, self.fc.bias)
         return self.fc(h)
+
+
+def model_from_state_dict(state: Dict[str, Tensor], compute_dtype: torch.dtype = torch.float32) -> MotionModel:
+    """A ``MotionModel`` with the hyper-parameters a checkpoint's
+    ``model_state`` implies, its parameters loaded (``predict`` needs no flag
+    that repeats what the file already says).  Input and hidden size from
+    ``weight_ih_l0`` / ``weight_hh_l0``, the cell from their row count (4 H:
+    LSTM, 3 H: GRU), the layers from the key count, ``_reverse`` keys mean
+    bidirectional, the classes from ``fc.weight``; DDP's ``module.`` prefix is
+    accepted."""
+    from ..train.checkpoint import adapt_state_dict_keys
+    keys = [k[len("module."):] if k.startswith("module.") else k for k in state]
+    if "lstm.weight_hh_l0" not in keys or "fc.weight" not in keys:
+        raise KeyError("not a motion model state: lstm.weight_hh_l0 / fc.weight missing")
+    get = lambda k: state[k] if k in state else state["module." + k]  # noqa: E731
+    w_ih, w_hh = get("lstm.weight_ih_l0"), get("lstm.weight_hh_l0")
+    hidden, rows = int(w_hh.shape[1]), int(w_hh.shape[0])
+    if rows not in (3 * hidden, 4 * hidden):
+        raise ValueError(f"weight_hh_l0 has {rows} rows for hidden size {hidden}: neither an LSTM nor a GRU")
+    bidirectional = any(k.endswith("_reverse") for k in keys)
+    layers = sum(1 for k in keys if k.startswith("lstm.weight_hh_l") and not k.endswith("_reverse"))
+    model = MotionModel(int(w_ih.shape[1]), hidden, layers, int(get("fc.weight").shape[0]),
+                        cell="lstm" if rows == 4 * hidden else "gru", compute_dtype=compute_dtype,
+                        bidirectional=bidirectional)
+    model.load_state_dict(adapt_state_dict_keys(dict(state), model))
+    return model

@@ -417,21 +417,48 @@ class Trainer:
         n_train = len(loader.dataset)
         return total_loss / n_train, total_correct / n_train
 
+    def _fused_eval(self):
+        """The one-launch inference step (train/fused_eval.py) where it serves
+        the model; None: ``_evaluate`` runs ``model.forward`` per batch
+        (``PDRNN_FUSED_EVAL=0`` forces that)."""
+        if os.environ.get("PDRNN_FUSED_EVAL", "1") == "0":
+            return None
+        if getattr(self, "_fused_ev", False) is False:
+            from . import fused_eval
+            self._fused_ev = fused_eval.MotionEvalStep(self.model) \
+                if fused_eval.supported(self.model, self.device) else None
+        return self._fused_ev
+
     @torch.no_grad()
     def _evaluate(self, data_loader, formatter: TrainingMessageFormatter, epoch: Optional[int] = None):
         self.model.eval()
         eval_loss = 0.0
         total_correct = 0
-        for batch in data_loader:
-            output, labels = self._forward(batch)
-            labels = labels.long().reshape(-1)
-            loss = self.loss_fn(output, labels)
-            stats = self.loss_fn.last_stats.cpu()
-            eval_loss += float(stats[0])
-            total_correct += int(stats[2])
-            if log.isEnabledFor(logging.DEBUG) or logging.getLogger().isEnabledFor(logging.DEBUG):
-                logging.debug(f"Model predicted {torch.argmax(output, dim=1).data}; "
-                              f"Correct was {labels.data}")
+        debug = log.isEnabledFor(logging.DEBUG) or logging.getLogger().isEnabledFor(logging.DEBUG)
+        fused = self._fused_eval()
+        if fused is not None:
+            # one launch per batch, the statistics summed on the device and
+            # read once for the whole evaluation
+            for batch in data_loader:
+                features, labels = batch[0], batch[1]
+                idx = batch[2] if len(batch) == 3 else None
+                _, pred = fused(features, labels, idx)
+                if debug:
+                    labels = labels.long().reshape(-1)
+                    logging.debug(f"Model predicted {pred.data}; "
+                                  f"Correct was {(labels if idx is None else labels.index_select(0, idx)).data}")
+            eval_loss, _, total_correct, _ = fused.result()
+        else:
+            for batch in data_loader:
+                output, labels = self._forward(batch)
+                labels = labels.long().reshape(-1)
+                loss = self.loss_fn(output, labels)
+                stats = self.loss_fn.last_stats.cpu()
+                eval_loss += float(stats[0])
+                total_correct += int(stats[2])
+                if debug:
+                    logging.debug(f"Model predicted {torch.argmax(output, dim=1).data}; "
+                                  f"Correct was {labels.data}")
         eval_loss /= len(data_loader)
         num_examples = len(data_loader.dataset)
         accuracy = float(total_correct) / num_examples
