@@ -1263,6 +1263,58 @@ void persist_check() {
 // Large-H LSTM layer (both directions in one launch per step).
 // ---------------------------------------------------------------------------
 
+// an optional tensor argument that was given (neither None nor undefined)
+bool present(const optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// its fp32 data, or null when it was not given
+const float* f32_or_null(const optional<Tensor>& t) {
+  if (!present(t)) return nullptr;
+  TORCH_CHECK(t->is_contiguous() && t->scalar_type() == at::kFloat, "f32 contiguous state or state grad expected");
+  return t->data_ptr<float>();
+}
+
+// Direction d's forward fields for a launch that starts at step t0 of
+// sequences holding T steps of ndir directions: hseq [T, B, ndir*H], cseq
+// [ndir, T, B, H], acts [ndir, T, B, 4H]; xp holds the launch's steps only,
+// [steps, B, ndir*4H].  The state entering t0 > 0 is step t0 - 1 of hseq /
+// cseq (one direction: a dense [B, H]), else h0 / c0 ([ndir, B, H] or absent).
+void fill_fwd_dir(PdrnnLstmLargeDir& dd, int d, int ndir, int64_t T, int64_t B, int64_t H, int64_t t0, const Tensor& xp,
+                  const Tensor& w, const optional<Tensor>& h0, const float* c0, const Tensor& hseq, const Tensor& cseq,
+                  const Tensor& acts) {
+  TORCH_CHECK(t0 == 0 || ndir == 1, "a time range resumes one direction only");
+  float* cs = cseq.data_ptr<float>() + d * T * B * H;
+  dd.w = eptr(w);
+  dd.xp = eptr(xp, d * 4 * H); dd.xp_sb = ndir * 4 * H; dd.xp_st = B * ndir * 4 * H;
+  dd.h0 = t0 > 0 ? eptr(hseq, (t0 - 1) * B * H) : present(h0) ? eptr(*h0, d * B * H) : nullptr;
+  dd.c0 = t0 > 0 ? cs + (t0 - 1) * B * H : c0 ? c0 + d * B * H : nullptr;
+  dd.hseq = eptrm(hseq, t0 * B * ndir * H + d * H); dd.hseq_sb = ndir * H; dd.hseq_st = B * ndir * H;
+  dd.cseq = cs + t0 * B * H;
+  dd.acts = eptrm(acts, (d * T + t0) * B * 4 * H);
+}
+
+// The same for the backward: dgates [ndir, T, B, 4H] like acts; dout holds the
+// launch's steps only, [steps, B, ndir*H] with any row strides; dhn / dcn / c0
+// [ndir, B, H] fp32 or null; carry / dh0 / dc0 [ndir, B, H] fp32.
+void fill_bwd_dir(PdrnnLstmLargeDir& dd, int d, int64_t T, int64_t B, int64_t H, int64_t t0, const Tensor& wt,
+                  const Tensor& cseq, const Tensor& acts, const float* c0, const Tensor& dgates,
+                  const optional<Tensor>& dout, const float* dhn, const float* dcn, const Tensor& carry,
+                  const Tensor& dh0, const Tensor& dc0) {
+  float* cs = cseq.data_ptr<float>() + d * T * B * H;
+  dd.wt = eptr(wt);
+  dd.c0 = t0 > 0 ? cs + (t0 - 1) * B * H : c0 ? c0 + d * B * H : nullptr;
+  dd.cseq = cs + t0 * B * H;
+  dd.acts = eptrm(acts, (d * T + t0) * B * 4 * H);
+  dd.dgates = eptrm(dgates, (d * T + t0) * B * 4 * H);
+  if (present(dout)) {
+    dd.dout = eptr(*dout, d * H); dd.dout_sb = dout->stride(1); dd.dout_st = dout->stride(0);
+  }
+  dd.dhn = dhn ? dhn + d * B * H : nullptr;
+  dd.dcn = dcn ? dcn + d * B * H : nullptr;
+  dd.dc_carry = carry.data_ptr<float>() + d * B * H;
+  dd.dh0 = dh0.data_ptr<float>() + d * B * H;
+  dd.dc0 = dc0.data_ptr<float>() + d * B * H;
+}
+
 // xp: [T, B, ndir*4H] (16-bit, bias included, gate-interleaved per direction)
 // w:  ndir x [4H, H] gate-interleaved W_hh;  h0: [ndir, B, H] 16-bit;  c0: [ndir, B, H] f32
 // returns hseq [T, B, ndir*H], cseq [ndir, T, B, H] f32, acts [ndir, T, B, 4H]
@@ -1288,24 +1340,13 @@ std::vector<Tensor> lstm_large_fwd(const Tensor& xp, const std::vector<Tensor>& 
   Tensor hseq = at::empty({T, B, ndir * H}, o16);
   Tensor cseq = at::empty({ndir, T, B, H}, o32);
   Tensor acts = at::empty({ndir, T, B, 4 * H}, o16);
-  const bool has_h0 = h0.has_value() && h0->defined();
-  const bool has_c0 = c0.has_value() && c0->defined();
-  if (has_h0) TORCH_CHECK(h0->is_contiguous() && large_dtype(*h0) == dt && h0->numel() == ndir * B * H, "h0 [ndir,B,H]");
-  if (has_c0) TORCH_CHECK(c0->is_contiguous() && c0->scalar_type() == at::kFloat && c0->numel() == ndir * B * H, "c0");
+  if (present(h0)) TORCH_CHECK(h0->is_contiguous() && large_dtype(*h0) == dt && h0->numel() == ndir * B * H, "h0 [ndir,B,H]");
+  if (present(c0)) TORCH_CHECK(c0->is_contiguous() && c0->scalar_type() == at::kFloat && c0->numel() == ndir * B * H, "c0");
   PdrnnLstmLargeStepArgs a{};
   a.B = (int)B; a.H = (int)H; a.T = (int)T; a.reverse_mask = (int)reverse_mask;
   TORCH_CHECK(cell == 0 || cell == 1, "cell: 0 = LSTM, 1 = GRU");
   a.cell = (int)cell;
-  for (int d = 0; d < ndir; ++d) {
-    PdrnnLstmLargeDir& dd = a.dir[d];
-    dd.w = eptr(w[d]);
-    dd.xp = eptr(xp, d * 4 * H); dd.xp_sb = ndir * 4 * H; dd.xp_st = B * ndir * 4 * H;
-    dd.h0 = has_h0 ? eptr(*h0, d * B * H) : nullptr;
-    dd.c0 = has_c0 ? c0->data_ptr<float>() + d * B * H : nullptr;
-    dd.hseq = eptrm(hseq, d * H); dd.hseq_sb = ndir * H; dd.hseq_st = B * ndir * H;
-    dd.cseq = cseq.data_ptr<float>() + d * T * B * H;
-    dd.acts = eptrm(acts, d * T * B * 4 * H);
-  }
+  for (int d = 0; d < ndir; ++d) fill_fwd_dir(a.dir[d], d, ndir, T, B, H, 0, xp, w[d], h0, f32_or_null(c0), hseq, cseq, acts);
   hipStream_t st = cur_stream();
   if (tile < 0 && rows_f32_on() && pdrnn_lstm_rows_f32_supported((int)H, dt)) {
     HIP_LAUNCH_CHECK(pdrnn_lstm_rows_f32(&a, ndir, 0, st));
@@ -1348,8 +1389,7 @@ std::vector<Tensor> lstm_large_bwd(const optional<Tensor>& dout, const optional<
   TORCH_CHECK(acts.is_contiguous() && acts.size(0) == ndir && acts.size(3) == 4 * H, "acts [ndir, T, B, 4H]");
   TORCH_CHECK(cseq.is_contiguous() && cseq.scalar_type() == at::kFloat, "cseq f32");
   for (auto& t : wt) TORCH_CHECK(t.is_contiguous() && t.size(0) == H && t.size(1) == 4 * H && large_dtype(t) == dt, "wt [H, 4H]");
-  const bool has_dout = dout.has_value() && dout->defined();
-  if (has_dout) {
+  if (present(dout)) {
     TORCH_CHECK(large_dtype(*dout) == dt && dout->dim() == 3 && dout->size(2) == ndir * H && dout->stride(2) == 1,
                 "dout [T, B, ndir*H]");
   }
@@ -1358,33 +1398,15 @@ std::vector<Tensor> lstm_large_bwd(const optional<Tensor>& dout, const optional<
   Tensor dgates = at::empty({ndir, T, B, 4 * H}, o16);
   Tensor carry = at::empty({ndir, B, H}, o32);
   Tensor dh0 = at::empty({ndir, B, H}, o32), dc0 = at::empty({ndir, B, H}, o32);
-  auto f32p = [](const optional<Tensor>& t) -> const float* {
-    if (!(t.has_value() && t->defined())) return nullptr;
-    TORCH_CHECK(t->is_contiguous() && t->scalar_type() == at::kFloat, "f32 contiguous state grad expected");
-    return t->data_ptr<float>();
-  };
-  const float* dhn_p = f32p(dhn);
-  const float* dcn_p = f32p(dcn);
-  const float* c0_p = f32p(c0);
+  const float* dhn_p = f32_or_null(dhn);
+  const float* dcn_p = f32_or_null(dcn);
+  const float* c0_p = f32_or_null(c0);
   PdrnnLstmLargeStepArgs a{};
   a.B = (int)B; a.H = (int)H; a.T = (int)T; a.reverse_mask = (int)reverse_mask;
   TORCH_CHECK(cell == 0 || cell == 1, "cell: 0 = LSTM, 1 = GRU");
   a.cell = (int)cell;
   for (int d = 0; d < ndir; ++d) {
-    PdrnnLstmLargeDir& dd = a.dir[d];
-    dd.wt = eptr(wt[d]);
-    dd.c0 = c0_p ? c0_p + d * B * H : nullptr;
-    dd.cseq = cseq.data_ptr<float>() + d * T * B * H;
-    dd.acts = eptrm(acts, d * T * B * 4 * H);
-    dd.dgates = eptrm(dgates, d * T * B * 4 * H);
-    if (has_dout) {
-      dd.dout = eptr(*dout, d * H); dd.dout_sb = dout->stride(1); dd.dout_st = dout->stride(0);
-    }
-    dd.dhn = dhn_p ? dhn_p + d * B * H : nullptr;
-    dd.dcn = dcn_p ? dcn_p + d * B * H : nullptr;
-    dd.dc_carry = carry.data_ptr<float>() + d * B * H;
-    dd.dh0 = dh0.data_ptr<float>() + d * B * H;
-    dd.dc0 = dc0.data_ptr<float>() + d * B * H;
+    fill_bwd_dir(a.dir[d], d, T, B, H, 0, wt[d], cseq, acts, c0_p, dgates, dout, dhn_p, dcn_p, carry, dh0, dc0);
   }
   const LargeBwdPlan plan = large_bwd_plan((int)B, (int)H, ndir, dt);
   a.splitk = plan.splitk;
@@ -1441,20 +1463,12 @@ void lstm_rows_fwd_range(const Tensor& xp, const Tensor& w, const optional<Tenso
   check_rows_range(hseq, H, T, B, "hseq");
   check_rows_range(cseq, H, T, B, "cseq");
   check_rows_range(acts, 4 * H, T, B, "acts");
-  if (h0.has_value() && h0->defined()) check_rows_range(*h0, H, 1, B, "h0");
-  if (c0.has_value() && c0->defined()) check_rows_range(*c0, H, 1, B, "c0");
+  if (present(h0)) check_rows_range(*h0, H, 1, B, "h0");
+  if (present(c0)) check_rows_range(*c0, H, 1, B, "c0");
   PdrnnLstmLargeStepArgs a{};
   a.B = (int)B; a.H = (int)H; a.T = (int)(t1 - t0); a.cell = (int)cell;
-  PdrnnLstmLargeDir& d = a.dir[0];
-  float* hs = hseq.data_ptr<float>();
-  float* cs = cseq.data_ptr<float>();
-  d.w = w.data_ptr<float>();
-  d.xp = xp.data_ptr<float>(); d.xp_sb = 4 * H; d.xp_st = B * 4 * H;
-  d.h0 = t0 > 0 ? hs + (t0 - 1) * B * H : (h0.has_value() && h0->defined() ? h0->data_ptr<float>() : nullptr);
-  d.c0 = t0 > 0 ? cs + (t0 - 1) * B * H : (c0.has_value() && c0->defined() ? c0->data_ptr<float>() : nullptr);
-  d.hseq = hs + t0 * B * H; d.hseq_sb = H; d.hseq_st = B * H;
-  d.cseq = cs + t0 * B * H;
-  d.acts = acts.data_ptr<float>() + t0 * B * 4 * H;
+  // (the whole-sequence layer with a time offset and one direction)
+  fill_fwd_dir(a.dir[0], 0, 1, T, B, H, t0, xp, w, h0, f32_or_null(c0), hseq, cseq, acts);
   HIP_LAUNCH_CHECK(pdrnn_lstm_rows_f32(&a, 1, 0, cur_stream()));
 }
 
@@ -1481,31 +1495,17 @@ void lstm_rows_bwd_range(const optional<Tensor>& dout, const optional<Tensor>& d
   check_rows_range(dh0, H, 1, B, "dh0");
   check_rows_range(dc0, H, 1, B, "dc0");
   check_rows_range(carry, H, 1, B, "carry");
-  if (dhn.has_value() && dhn->defined()) check_rows_range(*dhn, H, 1, B, "dhn");
-  if (dcn.has_value() && dcn->defined()) check_rows_range(*dcn, H, 1, B, "dcn");
-  if (c0.has_value() && c0->defined()) check_rows_range(*c0, H, 1, B, "c0");
-  const bool has_dout = dout.has_value() && dout->defined();
-  if (has_dout) {
+  if (present(dhn)) check_rows_range(*dhn, H, 1, B, "dhn");
+  if (present(dcn)) check_rows_range(*dcn, H, 1, B, "dcn");
+  if (present(c0)) check_rows_range(*c0, H, 1, B, "c0");
+  if (present(dout)) {
     TORCH_CHECK(dout->scalar_type() == at::kFloat && dout->dim() == 3 && dout->size(0) == t1 - t0 &&
                 dout->size(1) == B && dout->size(2) == H && dout->stride(2) == 1, "dout [t1 - t0, B, H] fp32");
   }
   PdrnnLstmLargeStepArgs a{};
   a.B = (int)B; a.H = (int)H; a.T = (int)(t1 - t0); a.cell = (int)cell;
-  PdrnnLstmLargeDir& d = a.dir[0];
-  const float* cs = cseq.data_ptr<float>();
-  d.wt = wt.data_ptr<float>();
-  d.c0 = t0 > 0 ? cs + (t0 - 1) * B * H : (c0.has_value() && c0->defined() ? c0->data_ptr<float>() : nullptr);
-  d.cseq = const_cast<float*>(cs) + t0 * B * H;
-  d.acts = acts.data_ptr<float>() + t0 * B * 4 * H;
-  d.dgates = dgates.data_ptr<float>() + t0 * B * 4 * H;
-  if (has_dout) {
-    d.dout = dout->data_ptr<float>(); d.dout_sb = dout->stride(1); d.dout_st = dout->stride(0);
-  }
-  d.dhn = dhn.has_value() && dhn->defined() ? dhn->data_ptr<float>() : nullptr;
-  d.dcn = dcn.has_value() && dcn->defined() ? dcn->data_ptr<float>() : nullptr;
-  d.dc_carry = carry.data_ptr<float>();
-  d.dh0 = dh0.data_ptr<float>();
-  d.dc0 = dc0.data_ptr<float>();
+  fill_bwd_dir(a.dir[0], 0, T, B, H, t0, wt, cseq, acts, f32_or_null(c0), dgates, dout, f32_or_null(dhn),
+               f32_or_null(dcn), carry, dh0, dc0);
   HIP_LAUNCH_CHECK(pdrnn_lstm_rows_f32(&a, 1, 1, cur_stream()));  // (the first step's cell backward included)
 }
 

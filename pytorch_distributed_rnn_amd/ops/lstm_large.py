@@ -19,11 +19,14 @@ products on v_mfma_f32_16x16x4_f32, e.g. the motion CLI with
 Semantics are torch.nn.LSTM's (gate order i, f, g, o; reference:
 src/motion/model.py:9 builds its model on nn.LSTM); parameters stay in the
 stock nn.LSTM layout -- the gate interleave is a per-call permutation.
+
+The GRU (ops/gru_large.py) rides on the same kernels and the same host code:
+the layer and pipelined-stack Functions, the fp32 weight-gradient helper and
+the stack driver here are written once against a ``Cell`` record.
 """
 from __future__ import annotations
 
-import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -40,55 +43,23 @@ def _tile() -> int:
     return tune_int("large_tile", -1)
 
 
-def supported(x: Tensor, hidden: int, num_layers: int, bidirectional: bool = False) -> bool:
-    if x.dtype not in (torch.bfloat16, torch.float16, torch.float32) or x.device.type != "cuda" or x.dim() != 3:
+# storage dtype code of the large-H bindings (large_dtype in csrc/bindings.cpp)
+_DTYPE_CODE = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
+
+
+def supported(x: Tensor, hidden: int, num_layers: int = 1, bidirectional: bool = False) -> bool:
+    """This path covers the shape (LSTM and GRU alike: ops/gru_large.py)."""
+    if x.dtype not in _DTYPE_CODE or x.device.type != "cuda" or x.dim() != 3:
         return False
     mod = _ext.native(x.device)
     return mod is not None and hasattr(mod, "lstm_large_fwd") and bool(mod.lstm_large_supported(hidden))
 
 
-def _mm_f32(a: Tensor, b: Tensor) -> Tensor:
-    """a @ b with fp32 output from 16-bit inputs (hipBLASLt fp32 accumulate)."""
-    try:
-        return torch.mm(a, b, out_dtype=torch.float32)
-    except (RuntimeError, TypeError):
-        return torch.mm(a.float(), b.float())
-
-
-def _mm_tn_f32(g: Tensor, x: Tensor, steps: int) -> Tensor:
-    """g^T x with fp32 output for g [K, M], x [K, N], K = steps * rows.
-
-    Weight-gradient GEMMs of small layers have a tiny output and a huge K
-    (fp32 motion model, H = 128, B = 1440, T = 128: 512 x 128 outputs, K =
-    184k), so a single library GEMM has too few output tiles to fill the GPU
-    (measured 632 us at 38 TF/s, `profiles/r2_fp32_large_h128.md`).  Those are
-    split along K at step boundaries into one strided-batched GEMM plus a sum."""
-    K, M = g.shape
-    N = x.shape[1]
-    c = 1
-    if M * N <= (1 << 20) and K >= (1 << 14) and steps > 1:
-        for d in range(min(steps, 128), 1, -1):
-            if steps % d == 0 and K // d >= 1024:
-                c = d
-                break
-    if c == 1:
-        return _mm_f32(g.t(), x)
-    gb = g.reshape(c, K // c, M).transpose(1, 2)
-    xb = x.reshape(c, K // c, N)
-    if g.dtype == torch.float32:
-        return torch.bmm(gb, xb).sum(0)
-    try:
-        return torch.bmm(gb, xb, out_dtype=torch.float32).sum(0)
-    except (RuntimeError, TypeError):
-        return _mm_f32(g.t(), x)
-
-
-def _addmm_f32_(c: Tensor, a: Tensor, b: Tensor) -> Tensor:
-    """c += a @ b, fp32 c, 16-bit a / b."""
-    try:
-        return c.copy_(torch.addmm(c, a, b, out_dtype=torch.float32))
-    except (RuntimeError, TypeError):
-        return c.add_(torch.mm(a.float(), b.float()))
+def _bwd_persistent(mod, B: int, H: int, ndir: int, cdt: torch.dtype, tile: int) -> bool:
+    """lstm_large_bwd would run this shape as one grid-synced persistent launch
+    (an extension without the query: assume so, i.e. never overlap it)."""
+    query = getattr(mod, "lstm_large_bwd_persistent", None)
+    return True if query is None else bool(query(B, H, ndir, _DTYPE_CODE[cdt], tile))
 
 
 def shadow(w: Tensor, kind: str, cdt: torch.dtype, hidden: int) -> Tensor:
@@ -178,6 +149,36 @@ def _bias_cat(weights, ndir: int, hidden: int, device) -> Tensor:
     return _sh.get(weights[0], ("bias", ndir, hidden), bs, alloc, build)
 
 
+class Cell(NamedTuple):
+    """What differs between the cells on this path; the layer, the pipelined
+    stack, the weight-gradient helper and the stack driver below are written
+    once against it (LSTM here, GRU in ops/gru_large.py).  Both cells ride on
+    the step kernels' four-column quad, so dgates is [.., 4H] for either;
+    column and row positions below are in units of H."""
+    cell: int            # id the bindings take (csrc/include/pdrnn/api.h: PdrnnLstmLargeStepArgs.cell)
+    gates: int           # gate rows of the parameters: W_ih [gates*H, I], W_hh [gates*H, H]
+    has_c: bool          # a cell state of its own (c0 / cseq / dcn / dc0); else the fp32 h rides in that slot
+    xcols: int           # dgates[:, :xcols*H] is the x side (dW_ih, dX)
+    hh_blocks: Tuple[Tuple[int, int, int], ...]  # (c0, c1, r0): dgates columns [c0, c1) -> dW_hh rows from r0
+    # db_ih is the row sums rs of the dW_ih pass; db_hh is the same tensor
+    # (None) or db_hh(rs, G [T*B, 4H], H, out) fills ``out`` [gates*H]
+    db_hh: Optional[Callable]
+    # shadows(weights, ndir, H, I, cdt, device) -> (projection stack [ndir*4H, I]
+    # gate-interleaved, folded fp32 bias [ndir*4H], and per direction the
+    # interleaved W_hh (forward step), W_ih as stored (dX) and W_hh^T (BPTT))
+    shadows: Callable
+    # 16-bit layers: backward16(ctx, dgates, dh0, dc0, hseq, h0c, x2, wih) ->
+    # the layer Function's gradients (the one place the cells' structure differs)
+    backward16: Callable
+
+
+def _lstm_shadows(weights, ndir: int, H: int, I: int, cdt, device):
+    w_ih = [weights[4 * d] for d in range(ndir)]
+    w_hh = [weights[4 * d + 1] for d in range(ndir)]
+    return (_shadow_cat(w_ih, cdt, H), _bias_cat(weights, ndir, H, device), [shadow(w, "i", cdt, H) for w in w_hh],
+            [shadow(w, "p", cdt, H) for w in w_ih], [shadow(w, "t", cdt, H) for w in w_hh])
+
+
 # ---------------------------------------------------------------------------
 # Cross-layer overlap in the fp32 backward: layer l's recurrence (90 of 256
 # CUs at the motion batch) needs only the layer above's dX, not its weight
@@ -246,13 +247,21 @@ def mark_ready(dx: Optional[Tensor]) -> Optional[Tensor]:
     return dx
 
 
-def final_hidden(hseq: Tensor, last: Sequence[int], H: int) -> Tensor:
-    """[ndir, B, H] final hidden states out of hseq [T, B, ndir*H]: one copy
-    per direction into a fresh tensor (no ATen concatenation kernel)."""
-    hn = hseq.new_empty(len(last), hseq.shape[1], H)
-    for d, t in enumerate(last):
-        hn[d].copy_(hseq[t, :, d * H:(d + 1) * H])
-    return hn
+def _final_states(cell: Cell, hs: Sequence[Tensor], cs: Sequence[Tensor], cdt) -> Tuple[Tensor, Optional[Tensor]]:
+    """The [B, H] final hidden states ``hs`` (one per direction or layer)
+    gathered into a fresh [n, B, H] tensor, and for a cell with a c state the
+    fp32 ``cs`` likewise, in the compute dtype.  The LSTM's two gathers are one
+    pack launch (ops/shadow.py); the GRU's is a copy per entry, as it always
+    was -- moving it onto the pack launch changes its launch sequence, which is
+    a change of its own."""
+    hn = hs[0].new_empty(len(hs), *hs[0].shape)
+    if not cell.has_c:
+        for k, h in enumerate(hs):
+            hn[k].copy_(h)
+        return hn, None
+    cn = cs[0].new_empty(len(cs), *cs[0].shape, dtype=cdt)
+    _sh.pack([_sh.job(hn[k], h) for k, h in enumerate(hs)] + [_sh.job(cn[k], c) for k, c in enumerate(cs)], hn.device)
+    return hn, cn
 
 
 class _StackStates(torch.autograd.Function):
@@ -295,116 +304,165 @@ def stack_layers(states: List[Tensor]) -> Tensor:
     return out
 
 
-class _LargeLSTMLayer(torch.autograd.Function):
-    """One layer, 1 or 2 directions.  x: [T, B, I] (compute dtype).
+def _cols(t: Tensor, c0: int, c1: int) -> Tensor:
+    """Columns [c0, c1) of a 2-D tensor: the tensor itself when that is all of
+    them (a view costs host time, and this path is bound by it)."""
+    return t if c0 == 0 and c1 == t.shape[1] else t[:, c0:c1]
 
-    weights: per direction (w_ih, w_hh, b_ih, b_hh), fp32 master parameters
-    (biases may be None)."""
+
+def _weight_grads(cell: Cell, G3: Tensor, hd: Tensor, h0: Optional[Tensor], xin: Tensor, d: int, t0: int, t1: int,
+                  dwih: Optional[Tensor] = None, dwhh: Optional[Tensor] = None, accumulate: bool = False,
+                  pad: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """Steps [t0, t1) of one direction's fp32 weight gradients, every product
+    on the fp32-product MFMA GEMM (kernels/gemm_f32.hip) -> (dW_ih, dW_hh, rs).
+
+    G3 [T, B, 4H]: the direction's dgates; hd [T, B, H]: its output sequence
+    (a strided view of hseq will do: no h_prev copy); h0 [B, H] or None;
+    xin [T, B, I]: the layer input.  dW_hh = sum_t dgates_t^T h_prev(t), block
+    by block of ``cell.hh_blocks``: h_prev(t) is h_{t-1} forward (d = 0) and
+    h_{t+1} reverse (d = 1), and the step next to the initial state pairs with
+    h0 as a second K segment.  dW_ih = dgates^T x over the x-side columns, with
+    rs, the row sums of that pass (the bias gradient), alongside.  ``dwih`` /
+    ``dwhh``: written in place (``accumulate``: added to; rs never is), fresh
+    tensors otherwise.  ``pad``: a narrow input goes through padded_cols
+    (needs ``dwih``)."""
+    T, B, H4 = G3.shape
+    H = H4 // 4
+    G = G3.view(T * B, H4)
+    if d == 0:
+        lo, hi, shift, edge, at_edge = max(t0, 1), t1, -1, 0, t0 == 0
+    else:
+        lo, hi, shift, edge, at_edge = t0, min(t1, T - 1), 1, T - 1, t1 == T
+    if dwhh is None:
+        dwhh = G3.new_empty(cell.gates * H, H)
+    if hi > lo:
+        Gs, hs = G[lo * B:hi * B], hd[lo + shift:hi + shift].reshape(-1, H)
+    g0 = G[edge * B:(edge + 1) * B] if at_edge and h0 is not None else None
+    for c0, c1, r0 in cell.hh_blocks:
+        out = dwhh if c1 - c0 == cell.gates else dwhh[r0 * H:(r0 + c1 - c0) * H]
+        seg = (_cols(g0, c0 * H, c1 * H), h0) if g0 is not None else None
+        if hi > lo:
+            gemm_f32(_cols(Gs, c0 * H, c1 * H), True, hs, True, pairs2=seg, out=out, accumulate=accumulate)
+        elif seg is not None:
+            gemm_f32(seg[0], True, seg[1], True, out=out, accumulate=accumulate)
+        elif not accumulate:
+            out.zero_()
+    x2 = xin.reshape(T * B, xin.shape[2])
+    Gx = _cols(G, 0, cell.xcols * H)
+    if t1 - t0 < T:
+        Gx, x2 = Gx[t0 * B:t1 * B], x2[t0 * B:t1 * B]
+    if pad and x2.shape[1] % 32:  # narrow input (motion: 9 features): whole, aligned column tiles
+        c, rs = gemm_f32(Gx, True, padded_cols(x2), True, rowsum=True)
+        dwih.add_(c[:, :x2.shape[1]]) if accumulate else dwih.copy_(c[:, :x2.shape[1]])
+    else:
+        dwih, rs = gemm_f32(Gx, True, x2, True, rowsum=True, out=dwih, accumulate=accumulate)
+    return dwih, dwhh, rs
+
+
+def _state_grads(ctx, dh0, dc0, h0_dtype, c0_dtype) -> List[Optional[Tensor]]:
+    """[dh0, dc0] for autograd: cast to the dtype the initial state came in
+    (a list of per-layer [B, H] is stacked first); None for a state that was
+    not given or needs no gradient (a detached carried state -- truncated
+    BPTT -- costs no stack or cast kernel)."""
+    out: List[Optional[Tensor]] = []
+    for k, (g, dtype) in enumerate(((dh0, h0_dtype), (dc0, c0_dtype)), 1):
+        if g is None or dtype is None or not ctx.needs_input_grad[k]:
+            out.append(None)
+        else:
+            out.append((torch.stack(g) if isinstance(g, list) else g).to(dtype))
+    return out
+
+
+class _LargeLayer(torch.autograd.Function):
+    """One layer of either cell, 1 or 2 directions.  x: [T, B, I] (compute
+    dtype); cfg: (cell, hidden, ndir, tile); weights: per direction (w_ih,
+    w_hh, b_ih, b_hh), fp32 master parameters (biases may be None).  Returns
+    (hseq, hn, cn), cn None for a cell without a c state."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, cfg, *weights):
-        ctx.set_materialize_grads(False)  # unused outputs: None, not a zero fill (run_recurrence)
-        hidden, ndir, tile = cfg
+        # unused outputs come back as None, not as a zero fill queued on the
+        # main stream after the ready event (run_recurrence)
+        ctx.set_materialize_grads(False)
+        cell, H, ndir, tile = cfg
         cdt = x.dtype
         T, B, I = x.shape
-        H = hidden
         mod = _ext.native(x.device)
-        w_ih = [weights[4 * d] for d in range(ndir)]
-        w_hh = [weights[4 * d + 1] for d in range(ndir)]
-        wih_p = _shadow_cat(w_ih, cdt, H)                                  # [ndir*4H, I]
-        bias_all = _bias_cat(weights, ndir, H, x.device)                   # fp32 [ndir*4H], interleaved
+        # forward in gate-interleaved order; backward in torch's gate-blocked
+        # order: W_ih as stored (dX GEMM), W_hh transposed (BPTT step GEMM)
+        proj, bias, whh_i, wih_p, wt = cell.shadows(weights, ndir, H, I, cdt, x.device)
         if cdt == torch.float32:  # fp32-product MFMA GEMM (kernels/gemm_f32.hip), fp32 bias in the epilogue
-            xp = gemm_f32(x.reshape(T * B, I), False, wih_p, False, bias=bias_all)[0]
-            xp = xp.view(T, B, ndir * 4 * H)
+            xp = gemm_f32(x.reshape(T * B, I), False, proj, False, bias=bias)[0]
         else:  # in-tree MFMA GEMM, fp32 bias added before the 16-bit rounding (ops/gemm.py)
-            xp = linear16(x.reshape(T * B, I), wih_p, bias_all).view(T, B, ndir * 4 * H)
-        whh_p = [shadow(w, "i", cdt, H) for w in w_hh]
+            xp = linear16(x.reshape(T * B, I), proj, bias)
+        xp = xp.view(T, B, ndir * 4 * H)
         h0c = h0.to(cdt).contiguous() if h0 is not None else None
-        c0c = c0.float().contiguous() if c0 is not None else None
+        s0 = c0 if cell.has_c else h0  # the fp32 state beside h: c, or the GRU's own h
+        s0 = s0.float().contiguous() if s0 is not None else None
         rev_mask = 2 if ndir == 2 else 0
-        hseq, cseq, acts = mod.lstm_large_fwd(xp, whh_p, h0c, c0c, H, rev_mask, tile, 0)
+        hseq, sseq, acts = mod.lstm_large_fwd(xp, whh_i, h0c, s0, H, rev_mask, tile, cell.cell)
         last = [T - 1, 0][:ndir]
-        # final h (out of hseq) and c (fp32 cseq -> compute dtype) of every
-        # direction: one pack launch instead of a copy each
-        hn = hseq.new_empty(ndir, B, H)
-        cn = cseq.new_empty(ndir, B, H, dtype=cdt)
-        _sh.pack([_sh.job(hn[d], hseq[last[d], :, d * H:(d + 1) * H]) for d in range(ndir)] +
-                 [_sh.job(cn[d], cseq[d, last[d]]) for d in range(ndir)], x.device)
-        # backward works in torch's gate-blocked order: W_ih as stored (dX GEMM),
-        # W_hh transposed (BPTT step GEMM), both 16-bit shadows
-        ctx.save_for_backward(x, hseq, cseq, acts, h0c, c0c, *[shadow(w, "p", cdt, H) for w in w_ih],
-                              *[shadow(w, "t", cdt, H) for w in w_hh])
-        ctx.cfg = (H, ndir, tile, rev_mask, [w is not None for w in weights], h0 is not None,
-                   c0 is not None, h0.dtype if h0 is not None else None,
-                   c0.dtype if c0 is not None else None)
-        ctx.params = weights  # (gradsink: the 16-bit backward may accumulate into their .grad)
+        hn, cn = _final_states(cell, [hseq[last[d], :, d * H:(d + 1) * H] for d in range(ndir)],
+                               [sseq[d, last[d]] for d in range(ndir)] if cell.has_c else (), cdt)
+        ctx.save_for_backward(x, hseq, sseq, acts, h0c, s0, *wih_p, *wt)
+        ctx.cfg = (cell, H, ndir, tile, rev_mask, [w is not None for w in weights],
+                   h0.dtype if h0 is not None else None, c0.dtype if cell.has_c and c0 is not None else None)
+        ctx.params = weights  # (gradsink: the LSTM's 16-bit backward may accumulate into their .grad)
         ctx.direct = gradsink.enabled()
         return hseq, hn, cn
 
     @staticmethod
     def backward(ctx, dhseq, dhn, dcn):
-        H, ndir, tile, rev_mask, has_w, has_h0, has_c0, h0_dtype, c0_dtype = ctx.cfg
-        x, hseq, cseq, acts, h0c, c0c, *ws = ctx.saved_tensors
-        wih, whh = ws[:ndir], ws[ndir:]
+        cell, H, ndir, tile, rev_mask, has_w, h0_dtype, c0_dtype = ctx.cfg
+        x, hseq, sseq, acts, h0c, s0, *ws = ctx.saved_tensors
+        wih, wt = ws[:ndir], list(ws[ndir:])                        # wt: [H, 4H], gate-blocked
         cdt = x.dtype
         T, B, I = x.shape
         mod = _ext.native(x.device)
-        wt = list(whh)                                              # [H, 4H], gate-blocked
 
         def bptt():
             dout = dhseq.to(cdt).contiguous() if dhseq is not None else None
             dhn_f = dhn.float().contiguous() if dhn is not None else None
             dcn_f = dcn.float().contiguous() if dcn is not None else None
-            return mod.lstm_large_bwd(dout, dhn_f, dcn_f, wt, cseq, acts, c0c, H, rev_mask, tile, 0)
+            return mod.lstm_large_bwd(dout, dhn_f, dcn_f, wt, sseq, acts, s0, H, rev_mask, tile, cell.cell)
 
-        persistent = bool(getattr(mod, "lstm_large_bwd_persistent", lambda *a: True)(
-            B, H, ndir, {torch.bfloat16: 0, torch.float16: 1}.get(cdt, 2), tile))
-        dgates, dh0, dc0 = run_recurrence(dhseq, bptt, [dhseq, dhn, dcn, cseq, acts, c0c, *wt], persistent)
-        grads: List[Optional[Tensor]] = []
-        dx = None
-        need_dx = ctx.needs_input_grad[0]
-        x2 = x.reshape(T * B, I)
+        dgates, dh0, dc0 = run_recurrence(dhseq, bptt, [dhseq, dhn, dcn, sseq, acts, s0, *wt],
+                                          _bwd_persistent(mod, B, H, ndir, cdt, tile))
         if cdt != torch.float32:
-            return _backward_gemms16(ctx, dgates, dh0, dc0, hseq, h0c, x2, wih)
-        # fp32 layers: every product on the fp32-product MFMA GEMM
-        # (kernels/gemm_f32.hip): dW_hh over shifted views of the output
-        # sequence with the initial-state pairing as a second K segment, dW_ih
-        # with db as the row sums of dgates^T in the same pass, dX of both
-        # directions in one launch (K segments) -- first, so the layer below
-        # can start its recurrence beside this layer's dW (run_recurrence)
-        if need_dx:
-            Gd = [dgates[d].view(T * B, 4 * H) for d in range(ndir)]
-            dx = gemm_f32(Gd[0], False, wih[0], True, pairs2=(Gd[1], wih[1]) if ndir > 1 else None)[0]
+            return cell.backward16(ctx, dgates, dh0, dc0, hseq, h0c, x.reshape(T * B, I), wih)
+        # fp32 layers.  dX of both directions in one launch (K segments) and
+        # first, so the layer below can start its recurrence beside this
+        # layer's dW GEMMs (run_recurrence); it is returned as the very tensor
+        # mark_ready tagged: a view would drop the ready event
+        dx = None
+        G3 = [dgates[d] for d in range(ndir)]
+        G = [g.view(T * B, 4 * H) for g in G3]
+        if ctx.needs_input_grad[0]:
+            Gx = [_cols(g, 0, cell.xcols * H) for g in G]
+            dx = gemm_f32(Gx[0], False, wih[0], True, pairs2=(Gx[1], wih[1]) if ndir > 1 else None)[0]
             dx = mark_ready(dx.view(T, B, I))
+        grads: List[Optional[Tensor]] = []
         for d in range(ndir):
-            G = dgates[d].view(T * B, 4 * H)                         # gate-blocked = parameter order
-            hd = hseq[:, :, d * H:(d + 1) * H]                       # strided view, row stride ndir*H
-            # dW_hh = sum_t dgates_t^T h_prev(t): forward h_prev(t) = h_{t-1},
-            # reverse h_{t+1}; the step next to the initial state pairs with h0
-            g0 = G[:B] if d == 0 else G[(T - 1) * B:]
-            seg2 = (g0, h0c[d]) if h0c is not None else None
-            if T > 1:
-                Gs = G[B:] if d == 0 else G[:(T - 1) * B]
-                hs = (hd[:-1] if d == 0 else hd[1:]).reshape((T - 1) * B, H)
-                dwhh = gemm_f32(Gs, True, hs, True, pairs2=seg2)[0]
-            elif seg2 is not None:
-                dwhh = gemm_f32(seg2[0], True, seg2[1], True)[0]
-            else:
-                dwhh = torch.zeros(4 * H, H, device=x.device, dtype=torch.float32)
-            dwih, db = gemm_f32(G, True, x2, True, rowsum=True)
-            grads += [dwih, dwhh, db if has_w[4 * d + 2] else None, db if has_w[4 * d + 3] else None]
-        # (a detached carried state -- truncated BPTT -- needs no cast kernels)
-        dh0_out = dh0.to(h0_dtype) if has_h0 and ctx.needs_input_grad[1] else None
-        dc0_out = dc0.to(c0_dtype) if has_c0 and ctx.needs_input_grad[2] else None
-        return (dx, dh0_out, dc0_out, None, *grads)
+            dwih, dwhh, dbih = _weight_grads(cell, G3[d], hseq[:, :, d * H:(d + 1) * H],
+                                             h0c[d] if h0c is not None else None, x, d, 0, T)
+            dbhh = dbih
+            if cell.db_hh is not None:
+                dbhh = cell.db_hh(dbih, G[d], H, dbih.new_empty(cell.gates * H))
+            grads += [dwih, dwhh, dbih if has_w[4 * d + 2] else None, dbhh if has_w[4 * d + 3] else None]
+        return (dx, *_state_grads(ctx, dh0, dc0 if cell.has_c else None, h0_dtype, c0_dtype), None, *grads)
 
 
 def _backward_gemms16(ctx, dgates, dh0, dc0, hseq, h0c, x2, wih):
     """16-bit layers: weight and input gradients on the in-tree MFMA GEMM
     (ops/gemm.py): dW_hh = sum_t dgates_t^T h_prev(t) with the initial-state
     pairing folded in as a second K segment, dW_ih = dG^T X, dX of both
-    directions in one launch (K segments), fp32 accumulation throughout."""
-    H, ndir, tile, rev_mask, has_w, has_h0, has_c0, h0_dtype, c0_dtype = ctx.cfg
+    directions in one launch (K segments), fp32 accumulation throughout.
+
+    The GRU's 16-bit backward (ops/gru_large.py:_backward_gemms16) is built
+    differently -- an h_prev concatenation instead of K-segment pairs, and no
+    gradsink; moving it onto this function changes its launches and speed, so
+    that is a change of its own."""
+    cell, H, ndir, tile, rev_mask, has_w, h0_dtype, c0_dtype = ctx.cfg
     T, B, I = ctx.saved_tensors[0].shape
     grads: List[Optional[Tensor]] = []
     Gs = []
@@ -441,9 +499,7 @@ def _backward_gemms16(ctx, dgates, dh0, dc0, hseq, h0c, x2, wih):
         db = col_sum(G)  # in-tree deterministic column sums (fp32 accumulation of the 16-bit G)
         grads += [dwih, dwhh, db if has_w[4 * d + 2] else None, db if has_w[4 * d + 3] else None]
     dx = mm_nk16([(Gs[d], wih[d]) for d in range(ndir)]).view(T, B, I) if ctx.needs_input_grad[0] else None
-    dh0_out = dh0.to(h0_dtype) if has_h0 and ctx.needs_input_grad[1] else None
-    dc0_out = dc0.to(c0_dtype) if has_c0 and ctx.needs_input_grad[2] else None
-    return (dx, dh0_out, dc0_out, None, *grads)
+    return (dx, *_state_grads(ctx, dh0, dc0, h0_dtype, c0_dtype), None, *grads)
 
 
 # ---------------------------------------------------------------------------
@@ -556,131 +612,143 @@ def pipeline_backward(streams, chunks, project, recur, finish) -> None:
                     finish(l)
 
 
-class _PipelinedLSTMStack(torch.autograd.Function):
-    """All layers of a unidirectional fp32 stack, chunk-pipelined (see above).
-    x: [T, B, I] fp32; h0 / c0: [L, B, H] or None; weights: nn.LSTM
-    ``_all_weights`` order, ``per`` (2 or 4) tensors per layer."""
+def _add_bias_sinks(rs: Tensor, bi: Optional[Tensor], bh: Optional[Tensor]) -> None:
+    """Direct mode (ops/gradsink.py): the row sums added into the flat
+    gradient views of b_ih and b_hh as they come out of the dW_ih pass."""
+    # (same storage too: two separately allocated gradients can sit side by
+    # side in the caching allocator)
+    if bi is not None and bh is not None and bh.data_ptr() == bi.data_ptr() + bi.numel() * 4 and \
+            bi.untyped_storage().data_ptr() == bh.untyped_storage().data_ptr():
+        # b_ih, b_hh adjacent in the flat gradient: one launch for both
+        torch.as_strided(bi, (2, bi.numel()), (bi.numel(), 1)).add_(rs)
+        return
+    for bg in (bi, bh):
+        if bg is not None:
+            bg.add_(rs)
+
+
+class _PipelinedStack(torch.autograd.Function):
+    """All layers of a unidirectional fp32 stack of either cell,
+    chunk-pipelined (see above).  x: [T, B, I] fp32; h0 / c0: [L, B, H] or None;
+    cfg: (cell, hidden, layers, per, chunks); weights: nn.LSTM / nn.GRU
+    ``_all_weights`` order, ``per`` (2 or 4) tensors per layer.  Returns
+    (hseq of the last layer, hn, cn), cn None for a cell without a c state."""
 
     @staticmethod
     def forward(ctx, x, h0, c0, cfg, *weights):
         ctx.set_materialize_grads(False)
-        H, L, per, chunks = cfg
+        cell, H, L, per, chunks = cfg
         T, B, I = x.shape
         dev = x.device
-        f32 = torch.float32
-        mod = _ext.native(dev)
         lw = [list(weights[l * per:(l + 1) * per]) + ([None, None] if per == 2 else []) for l in range(L)]
-        wih = [shadow(w[0], "i", f32, H) for w in lw]                 # [4H, I_l] gate-interleaved
-        whh = [shadow(w[1], "i", f32, H) for w in lw]
-        bias = [_bias_cat(w, 1, H, dev) for w in lw]
+        # per layer: projection stack [4H, I_l], folded bias, then one-entry
+        # lists of the interleaved W_hh, W_ih as stored and W_hh^T
+        proj, bias, whh_i, wih_p, wt = zip(*[cell.shadows(lw[l], 1, H, I if l == 0 else H, torch.float32, dev)
+                                             for l in range(L)])
         h0s = [h0[l].float().contiguous() if h0 is not None else None for l in range(L)]
-        c0s = [c0[l].float().contiguous() if c0 is not None else None for l in range(L)]
+        # the fp32 state beside h: c, or the GRU's own h (the same tensors)
+        s0s = [c0[l].float().contiguous() if c0 is not None else None for l in range(L)] if cell.has_c else h0s
         hseq = [x.new_empty(T, B, H) for _ in range(L)]
-        cseq = [x.new_empty(T, B, H) for _ in range(L)]
+        sseq = [x.new_empty(T, B, H) for _ in range(L)]
         acts = [x.new_empty(T, B, 4 * H) for _ in range(L)]
-        xps = [gemm_f32(x.reshape(T * B, I), False, wih[0], False, bias=bias[0])[0].view(T, B, 4 * H)]
+        xps = [gemm_f32(x.reshape(T * B, I), False, proj[0], False, bias=bias[0])[0].view(T, B, 4 * H)]
         xps += [x.new_empty(T, B, 4 * H) for _ in range(1, L)]
         rec = pipeline_streams(dev, L)
+        fwd_range, cid = _ext.native(dev).lstm_rows_fwd_range, cell.cell
 
         def project(l, t0, t1):  # this chunk's input projection
-            gemm_f32(hseq[l - 1][t0:t1].view(-1, H), False, wih[l], False, bias=bias[l],
+            gemm_f32(hseq[l - 1][t0:t1].view(-1, H), False, proj[l], False, bias=bias[l],
                      out=xps[l][t0:t1].view(-1, 4 * H))
 
         def recur(l, t0, t1):
-            mod.lstm_rows_fwd_range(xps[l][t0:t1], whh[l], h0s[l], c0s[l], hseq[l], cseq[l], acts[l], t0, t1, 0)
+            fwd_range(xps[l][t0:t1], whh_i[l][0], h0s[l], s0s[l], hseq[l], sseq[l], acts[l], t0, t1, cid)
 
         pipeline_forward(rec, chunks, project, recur)
         pipeline_join(rec)
-        # final h and c of every layer: one pack launch (ops/shadow.py)
-        hn = hseq[0].new_empty(L, *hseq[0].shape[1:])
-        cn = cseq[0].new_empty(L, *cseq[0].shape[1:])
-        _sh.pack([_sh.job(hn[l], hq[T - 1]) for l, hq in enumerate(hseq)] +
-                 [_sh.job(cn[l], cq[T - 1]) for l, cq in enumerate(cseq)], x.device)
-        ctx.save_for_backward(x, *hseq, *cseq, *acts, *[shadow(w[0], "p", f32, H) for w in lw],
-                              *[shadow(w[1], "t", f32, H) for w in lw])
-        ctx.states = (h0s, c0s)
-        ctx.params = lw  # (gradsink: the backward may accumulate into their .grad itself)
+        hn, cn = _final_states(cell, [hq[T - 1] for hq in hseq], [sq[T - 1] for sq in sseq] if cell.has_c else (),
+                               torch.float32)
+        ctx.save_for_backward(x, *hseq, *sseq, *acts, *[w[0] for w in wih_p], *[w[0] for w in wt])
+        ctx.states = (h0s, s0s)
+        # (gradsink, LSTM only: the backward may accumulate into the parameters' .grad itself)
+        ctx.params = lw if cell.has_c else None
         ctx.direct = gradsink.enabled()
-        ctx.cfg = (H, L, per, chunks, [[w is not None for w in ws] for ws in lw],
-                   h0.dtype if h0 is not None else None, c0.dtype if c0 is not None else None)
+        ctx.cfg = (cell, H, L, per, chunks, [[w is not None for w in ws] for ws in lw],
+                   h0.dtype if h0 is not None else None, c0.dtype if cell.has_c and c0 is not None else None)
         return hseq[L - 1], hn, cn
 
     @staticmethod
     def backward(ctx, dhseq, dhn, dcn):
-        H, L, per, chunks, has_w, h0_dtype, c0_dtype = ctx.cfg
-        h0s, c0s = ctx.states
+        cell, H, L, per, chunks, has_w, h0_dtype, c0_dtype = ctx.cfg
+        h0s, s0s = ctx.states
         sv = ctx.saved_tensors
         x = sv[0]
-        hseq, cseq, acts = sv[1:1 + L], sv[1 + L:1 + 2 * L], sv[1 + 2 * L:1 + 3 * L]
-        wp, wt = sv[1 + 3 * L:1 + 4 * L], sv[1 + 4 * L:1 + 5 * L]
+        hseq, sseq, acts, wp, wt = (sv[1 + k * L:1 + (k + 1) * L] for k in range(5))
         T, B, I = x.shape
         dev = x.device
-        mod = _ext.native(dev)
+        R, xc = cell.gates * H, cell.xcols * H
         dgates = [x.new_empty(T, B, 4 * H) for _ in range(L)]
         douts = [x.new_empty(T, B, H) for _ in range(L - 1)]
         douts.append(dhseq.float().contiguous() if dhseq is not None else None)
         dhb = [x.new_empty(B, H) for _ in range(L)]  # gradients leaving a chunk's first step
-        dcb = [x.new_empty(B, H) for _ in range(L)]
+        dcb = [x.new_empty(B, H) for _ in range(L)]  # (the kernel's dc0 slot; a cell without a c state leaves it unused)
         carry = [x.new_empty(B, H) for _ in range(L)]
         dhn_l = [dhn[l].float().contiguous() if dhn is not None else None for l in range(L)]
         dcn_l = [dcn[l].float().contiguous() if dcn is not None else None for l in range(L)]
         ins = [x] + list(hseq[:-1])  # each layer's input sequence
         # direct mode (ops/gradsink.py): a layer whose w_ih / w_hh (and biases)
         # all have flat .grad views accumulates into them in the GEMM epilogue
-        sinks = [[gradsink.sink(w, ctx.direct) for w in ctx.params[l]] for l in range(L)]
-        direct = [all(sk is not None for sk, w in zip(sinks[l], ctx.params[l]) if w is not None)
-                  for l in range(L)]
-        dwih = [sinks[l][0] if direct[l] else x.new_empty(4 * H, t.shape[2]) for l, t in enumerate(ins)]
-        dwhh = [sinks[l][1] if direct[l] else x.new_empty(4 * H, H) for l in range(L)]
-        db = [x.new_empty(4 * H) for _ in range(L)]
+        direct = [False] * L
+        if ctx.params is not None:
+            sinks = [[gradsink.sink(w, ctx.direct) for w in ws] for ws in ctx.params]
+            direct = [all(sk is not None for sk, w in zip(sinks[l], ctx.params[l]) if w is not None) for l in range(L)]
+        dwih = [sinks[l][0] if direct[l] else x.new_empty(R, t.shape[2]) for l, t in enumerate(ins)]
+        dwhh = [sinks[l][1] if direct[l] else x.new_empty(R, H) for l in range(L)]
+        dbih = [x.new_empty(R) for _ in range(L)]
+        dbhh = [x.new_empty(R) for _ in range(L)] if cell.db_hh is not None else dbih
         rec = pipeline_streams(dev, L)
+        bwd_range, cid, has_c = _ext.native(dev).lstm_rows_bwd_range, cell.cell, cell.has_c
 
         def project(l, t0, t1):  # this chunk's dout = dX of the layer above
             # (one K slice: split-K partials and their sum beside the
             # recurrences cost more than they recover, profiles/r4/pipe/p6_*)
-            gemm_f32(dgates[l + 1][t0:t1].view(-1, 4 * H), False, wp[l + 1], True, out=douts[l][t0:t1].view(-1, H),
-                     splitk=1)
+            gemm_f32(_cols(dgates[l + 1][t0:t1].view(-1, 4 * H), 0, xc), False, wp[l + 1], True,
+                     out=douts[l][t0:t1].view(-1, H), splitk=1)
 
         def recur(l, first, t0, t1):
             dout = douts[l][t0:t1] if douts[l] is not None else None
-            mod.lstm_rows_bwd_range(dout, dhn_l[l] if first else dhb[l], dcn_l[l] if first else dcb[l], wt[l],
-                                    cseq[l], acts[l], c0s[l], dgates[l], dhb[l], dcb[l], carry[l], t0, t1, 0)
+            dc_in = (dcn_l[l] if first else dcb[l]) if has_c else None
+            bwd_range(dout, dhn_l[l] if first else dhb[l], dc_in, wt[l], sseq[l], acts[l], s0s[l], dgates[l], dhb[l],
+                      dcb[l], carry[l], t0, t1, cid)
 
         def finish(l):  # the layer's recurrence is done: its weight gradients, on its stream
-            # (direct mode: the row sums are added into the bias gradients as
-            # they come out of the dW_ih pass, no copy into db first)
-            rs = _chunk_weight_grads(dwih[l], dwhh[l], None if direct[l] else db[l], dgates[l], hseq[l], h0s[l],
-                                     ins[l], 0, T, not direct[l], db_first=True)
-            if direct[l]:
-                db[l] = rs
-                bi, bh = sinks[l][2], sinks[l][3]
-                # (same storage too: two separately allocated gradients can sit
-                # side by side in the caching allocator -- ADVICE r5)
-                if bi is not None and bh is not None and bh.data_ptr() == bi.data_ptr() + bi.numel() * 4 and \
-                        bi.untyped_storage().data_ptr() == bh.untyped_storage().data_ptr():
-                    # b_ih, b_hh adjacent in the flat gradient: one launch for both
-                    torch.as_strided(bi, (2, bi.numel()), (bi.numel(), 1)).add_(db[l])
-                else:
-                    for bg in (bi, bh):
-                        if bg is not None:
-                            bg.add_(db[l])
+            _, _, rs = _weight_grads(cell, dgates[l], hseq[l], h0s[l], ins[l], 0, 0, T, dwih=dwih[l], dwhh=dwhh[l],
+                                     accumulate=direct[l], pad=True)
+            if direct[l]:  # (no copy into dbih first)
+                _add_bias_sinks(rs, sinks[l][2], sinks[l][3])
+                return
+            dbih[l].copy_(rs)
+            if cell.db_hh is not None:
+                cell.db_hh(rs, dgates[l].view(T * B, 4 * H), H, dbhh[l])
 
         pipeline_backward(rec, chunks, project, recur, finish)
         dx = None
         if ctx.needs_input_grad[0]:  # (layer 0's stream is the caller's)
-            dx = gemm_f32(dgates[0].view(T * B, 4 * H), False, wp[0], True)[0].view(T, B, I)
+            dx = gemm_f32(_cols(dgates[0].view(T * B, 4 * H), 0, xc), False, wp[0], True)[0].view(T, B, I)
         pipeline_join(rec)
         grads: List[Optional[Tensor]] = []
         for l in range(L):
             if direct[l]:  # already accumulated into the parameters' .grad
-                grads += [None, None] + ([None, None] if per == 4 else [])
+                grads += [None] * per
                 continue
             grads += [dwih[l], dwhh[l]]
             if per == 4:
-                grads += [db[l] if has_w[l][2] else None, db[l] if has_w[l][3] else None]
-        dh0 = torch.stack(dhb).to(h0_dtype) if h0_dtype is not None else None
-        dc0 = torch.stack(dcb).to(c0_dtype) if c0_dtype is not None else None
-        return (dx, dh0, dc0, None, *grads)
+                grads += [dbih[l] if has_w[l][2] else None, dbhh[l] if has_w[l][3] else None]
+        return (dx, *_state_grads(ctx, dhb, dcb if has_c else None, h0_dtype, c0_dtype), None, *grads)
+
+
+# the name this Function had while it served the LSTM alone: code that wraps
+# ``_PipelinedLSTMStack.apply`` to see the pipelined path run keeps working
+_PipelinedLSTMStack = _PipelinedStack
 
 
 def padded_cols(x2: Tensor, mult: int = 32) -> Tensor:
@@ -712,53 +780,35 @@ _PADDED: dict = {}
 
 
 def _chunk_weight_grads(dwih: Tensor, dwhh: Tensor, db: Optional[Tensor], G3: Tensor, hd: Tensor, h0: Optional[Tensor],
-                        xin: Tensor, t0: int, t1: int, first: bool, db_first: Optional[bool] = None) -> Tensor:
-    """Steps [t0, t1) of one unidirectional fp32 layer's dW_ih, dW_hh and db,
-    written (first chunk) or accumulated into the fp32 outputs: dW_hh pairs
-    dgates_t with h_{t-1} (h0 at t = 0), dW_ih dgates_t with the layer input,
-    db = the row sums of the dW_ih pass."""
-    H4 = G3.shape[2]
-    H = H4 // 4
-    lo = max(t0, 1)
-    seg0 = (G3[0], h0) if t0 == 0 and h0 is not None else None
-    if t1 > lo:
-        gemm_f32(G3[lo:t1].view(-1, H4), True, hd[lo - 1:t1 - 1].reshape(-1, H), True, pairs2=seg0, out=dwhh,
-                 accumulate=not first)
-    elif seg0 is not None:
-        gemm_f32(seg0[0], True, seg0[1], True, out=dwhh, accumulate=not first)
-    elif first:
-        dwhh.zero_()
-    x2 = xin[t0:t1].reshape(-1, xin.shape[2])
-    if x2.shape[1] % 32:  # narrow input (motion: 9 features): whole, aligned column tiles
-        c, rs = gemm_f32(G3[t0:t1].view(-1, H4), True, padded_cols(x2), True, rowsum=True)
-        dwih.copy_(c[:, :x2.shape[1]]) if first else dwih.add_(c[:, :x2.shape[1]])
-    else:
-        _, rs = gemm_f32(G3[t0:t1].view(-1, H4), True, x2, True, rowsum=True, out=dwih, accumulate=not first)
-    if db is None:  # the caller takes the row sums as they are
+                        xin: Tensor, t0: int, t1: int, first: bool) -> Tensor:
+    """Steps [t0, t1) of one unidirectional fp32 LSTM layer's dW_ih, dW_hh and
+    db, written (first chunk) or accumulated into the fp32 outputs
+    (_weight_grads, chunk by chunk; ``db`` None: the row sums as they are)."""
+    rs = _weight_grads(LSTM, G3, hd, h0, xin, 0, t0, t1, dwih=dwih, dwhh=dwhh, accumulate=not first, pad=True)[2]
+    if db is None:
         return rs
-    if first if db_first is None else db_first:
-        db.copy_(rs)
-    else:
-        db.add_(rs)
-    return db
+    return db.copy_(rs) if first else db.add_(rs)
 
 
-def lstm_large_forward(x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optional[Tensor],
-                       c0: Optional[Tensor], *, hidden: int, num_layers: int, batch_first: bool,
-                       bidirectional: bool = False, dropout: float = 0.0,
-                       training: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
-    """Stacked (bi)LSTM on the MFMA step kernels; nn.LSTM-compatible outputs.
+# gates i, f, g, o; dgates is gate-blocked, i.e. in parameter order throughout
+LSTM = Cell(cell=0, gates=4, has_c=True, xcols=4, hh_blocks=((0, 4, 0),), db_hh=None, shadows=_lstm_shadows,
+            backward16=_backward_gemms16)
 
-    ``weights``: nn.LSTM ``_all_weights`` order (per layer and direction
-    w_ih, w_hh[, b_ih, b_hh])."""
+
+def large_forward(cell: Cell, x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optional[Tensor],
+                  c0: Optional[Tensor], *, hidden: int, num_layers: int, batch_first: bool, bidirectional: bool = False,
+                  dropout: float = 0.0, training: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """A stacked (bidirectional) RNN of ``cell`` on the MFMA step kernels ->
+    (out, hn, cn) as nn.LSTM / nn.GRU return them (cn None without a c state).
+
+    ``weights``: ``_all_weights`` order (per layer and direction w_ih,
+    w_hh[, b_ih, b_hh])."""
     ndir = 2 if bidirectional else 1
     per = len(weights) // (num_layers * ndir)
-    seq = x.transpose(0, 1) if batch_first else x
-    seq = seq.contiguous()  # (a no-op for an index-gathered batch: see lstm_forward)
-    B = seq.shape[1]
+    seq = (x.transpose(0, 1) if batch_first else x).contiguous()  # (a no-op for an index-gathered batch: see lstm_forward)
     if pipeline_ok(seq, hidden, num_layers, bidirectional, dropout, training):
-        out, hn, cn = _PipelinedLSTMStack.apply(seq, h0, c0, (hidden, num_layers, per, pipeline_chunks(seq.shape[0])),
-                                                *weights)
+        out, hn, cn = _PipelinedStack.apply(seq, h0, c0, (cell, hidden, num_layers, per, pipeline_chunks(seq.shape[0])),
+                                            *weights)
         return (out.transpose(0, 1) if batch_first else out), hn, cn
     tile = _tile()
     hns, cns = [], []
@@ -771,7 +821,7 @@ def lstm_large_forward(x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optio
             ws += chunk
         h0l = h0[l * ndir:(l + 1) * ndir] if h0 is not None else None
         c0l = c0[l * ndir:(l + 1) * ndir] if c0 is not None else None
-        seq, hn, cn = _LargeLSTMLayer.apply(seq, h0l, c0l, (hidden, ndir, tile), *ws)
+        seq, hn, cn = _LargeLayer.apply(seq, h0l, c0l, (cell, hidden, ndir, tile), *ws)
         hns.append(hn)
         cns.append(cn)
         if dropout > 0 and training and l < num_layers - 1:
@@ -779,5 +829,14 @@ def lstm_large_forward(x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optio
     out = seq.transpose(0, 1) if batch_first else seq
     if num_layers == 1:
         return out, hns[0], cns[0]
+    if not cell.has_c:  # (slice copies, as the GRU always stacked its states; _StackStates is one pack launch)
+        return out, stack_layers(hns), None
     hn, cn = _StackStates.apply(num_layers, *hns, *cns)
     return out, hn, cn
+
+
+def lstm_large_forward(x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optional[Tensor],
+                       c0: Optional[Tensor], **kw) -> Tuple[Tensor, Tensor, Tensor]:
+    """Stacked (bi)LSTM on the MFMA step kernels; nn.LSTM-compatible outputs
+    (large_forward's keywords)."""
+    return large_forward(LSTM, x, weights, h0, c0, **kw)

@@ -96,3 +96,34 @@ def test_large_gru_no_bias_no_state():
     out_r.sum().backward()
     for (n, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
         assert _rel(p.grad, q.grad) < 4e-2, n
+
+
+@pytest.mark.parametrize("state", [False, True])
+def test_large_gru_single_step_matches_fp64(state):
+    """T = 1, bidirectional, against the fp64 nn.GRU: no step has a previous
+    output, so dW_hh is the h0 pairing alone, or zero without an initial state
+    (then the reference's is exactly zero too and _rel is 0 / eps)."""
+    dt, (B, T, I, H) = torch.bfloat16, (5, 1, 9, 64)
+    m, _ = _pair(I, H, 1, True, dt, seed=9)
+    ref = torch.nn.GRU(I, H, 1, batch_first=True, bidirectional=True).double().cuda()
+    with torch.no_grad():
+        for (_, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
+            q.copy_(p.double())
+    x = torch.randn(B, T, I, device="cuda").to(dt)
+    assert gru_large.supported(x, H)
+    h0 = (0.5 * torch.randn(2, B, H, device="cuda")).to(dt) if state else None
+    xa, xr = x.clone().requires_grad_(True), x.double().requires_grad_(True)
+    h0a = h0.clone().requires_grad_(True) if state else None
+    h0r = h0.double().requires_grad_(True) if state else None
+    out, hn = m(xa, h0a)
+    out_r, hn_r = ref(xr, h0r)
+    assert out.dtype == dt and out.shape == out_r.shape and hn.shape == hn_r.shape
+    assert _rel(out, out_r) < 2e-2 and _rel(hn, hn_r) < 2e-2
+    g, gh = torch.randn_like(out_r), torch.randn_like(hn_r)
+    ((out.double() * g).sum() + (hn.double() * gh).sum()).backward()
+    ((out_r * g).sum() + (hn_r * gh).sum()).backward()
+    assert _rel(xa.grad, xr.grad) < 4e-2
+    if state:
+        assert _rel(h0a.grad, h0r.grad) < 4e-2
+    for (n, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
+        assert _rel(p.grad, q.grad) < 4e-2, n

@@ -278,3 +278,35 @@ def test_embedding_bwd_large_vocab_uses_library_sort():
     dw = mod.embedding_bwd(g, idx, V, -1)
     ref = torch.zeros(V, D, device="cuda").index_add_(0, idx, g)
     torch.testing.assert_close(dw, ref, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("state", [False, True])
+def test_large_lstm_single_step_matches_fp64(state):
+    """T = 1, bidirectional bf16, against the fp64 nn.LSTM at the tolerances of
+    test_large_lstm_matches_torch: no step has a previous output, so dW_hh is
+    the h0 pairing alone, or zero without an initial state (then the
+    reference's is exactly zero too and _rel is 0 / eps)."""
+    torch.manual_seed(9)
+    dt, (B, T, I, H) = torch.bfloat16, (5, 1, 9, 64)
+    m = LSTM(I, H, 1, batch_first=True, bidirectional=True).cuda()
+    with torch.no_grad():
+        for p in m.parameters():
+            p.copy_(p.to(dt).float())
+    ref = _ref_model(m).double()
+    x = torch.randn(B, T, I, device="cuda").to(dt)
+    s0 = [(0.5 * torch.randn(2, B, H, device="cuda")).to(dt) for _ in range(2)] if state else None
+    xa, xr = x.clone().requires_grad_(True), x.double().requires_grad_(True)
+    s0a = tuple(s.clone().requires_grad_(True) for s in s0) if state else None
+    s0r = tuple(s.double().requires_grad_(True) for s in s0) if state else None
+    out, (hn, cn) = m(xa, s0a)
+    out_r, (hn_r, cn_r) = ref(xr, s0r)
+    assert out.dtype == dt and out.shape == out_r.shape
+    assert _rel(out, out_r) < 2e-2 and _rel(hn, hn_r) < 2e-2 and _rel(cn, cn_r) < 2e-2
+    g, gh, gc = torch.randn_like(out_r), torch.randn_like(hn_r), torch.randn_like(cn_r)
+    ((out.double() * g).sum() + (hn.double() * gh).sum() + (cn.double() * gc).sum()).backward()
+    ((out_r * g).sum() + (hn_r * gh).sum() + (cn_r * gc).sum()).backward()
+    assert _rel(xa.grad, xr.grad) < 4e-2
+    if state:
+        assert _rel(s0a[0].grad, s0r[0].grad) < 4e-2 and _rel(s0a[1].grad, s0r[1].grad) < 4e-2
+    for (n, p), (_, q) in zip(m.named_parameters(), ref.named_parameters()):
+        assert _rel(p.grad, q.grad) < 4e-2, n

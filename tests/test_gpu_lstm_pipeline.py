@@ -1,12 +1,12 @@
-"""Stacked-layer chunk pipeline of the fp32 H = 128 LSTM (ops/lstm_large.py
-_PipelinedLSTMStack on lstm_rows_fwd_range / lstm_rows_bwd_range) against the
+"""Stacked-layer chunk pipeline of the fp32 H = 128 LSTM and GRU (ops/lstm_large.py
+_PipelinedStack on lstm_rows_fwd_range / lstm_rows_bwd_range) against the
 whole-sequence per-layer path and an fp64 torch reference."""
 import pytest
 import torch
 
 from pytorch_distributed_rnn_amd import _ext
 from pytorch_distributed_rnn_amd.models.rnn import LSTM
-from pytorch_distributed_rnn_amd.ops import lstm_large
+from pytorch_distributed_rnn_amd.ops import gru_large, lstm_large
 
 from _tune import set_tune
 
@@ -16,6 +16,21 @@ pytestmark = pytest.mark.gpu
 def _rel(a, b):
     a, b = a.detach().double(), b.detach().double()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def _count_pipelined(monkeypatch, cell):
+    """The list that grows by one per run of the pipelined stack, which must
+    be a run for ``cell`` (the one Function serves both)."""
+    calls = []
+    orig = lstm_large._PipelinedStack.apply
+
+    def apply(*a):  # (x, h0, c0, (cell, ...), *weights)
+        assert a[3][0] is cell
+        calls.append(1)
+        return orig(*a)
+
+    monkeypatch.setattr(lstm_large._PipelinedStack, "apply", apply)
+    return calls
 
 
 def _run(m, x, h0, c0, g):
@@ -48,9 +63,7 @@ def test_pipeline_matches_whole_sequence_and_fp64(L, chunks, B, T, I, bias, stat
     c0 = torch.randn(L, B, H, device="cuda") if state else None
     g = torch.randn(B, T, H, device="cuda")
     set_tune(monkeypatch, large_chunks=str(chunks))
-    calls = []
-    orig = lstm_large._PipelinedLSTMStack.apply
-    monkeypatch.setattr(lstm_large._PipelinedLSTMStack, "apply", lambda *a: calls.append(1) or orig(*a))
+    calls = _count_pipelined(monkeypatch, lstm_large.LSTM)
     pipe = _run(m, x, h0, c0, g)
     assert calls, "the pipelined stack did not run"
     set_tune(monkeypatch, large_pipe="0")
@@ -131,7 +144,6 @@ def _run_gru(m, x, h0, g):
                                                        (2, 1, 16, 5, 9, True, True), (2, 12, 20, 12, 9, True, True)])
 def test_gru_pipeline_matches_whole_sequence_and_fp64(L, chunks, B, T, I, bias, state, monkeypatch):
     from pytorch_distributed_rnn_amd.models.rnn import GRU
-    from pytorch_distributed_rnn_amd.ops import gru_large
     torch.manual_seed(8)
     H = 128
     m = GRU(I, H, L, batch_first=True, bias=bias).cuda()
@@ -139,9 +151,7 @@ def test_gru_pipeline_matches_whole_sequence_and_fp64(L, chunks, B, T, I, bias, 
     h0 = torch.randn(L, B, H, device="cuda") if state else None
     g = torch.randn(B, T, H, device="cuda")
     set_tune(monkeypatch, large_chunks=str(chunks))
-    calls = []
-    orig = gru_large._PipelinedGRUStack.apply
-    monkeypatch.setattr(gru_large._PipelinedGRUStack, "apply", lambda *a: calls.append(1) or orig(*a))
+    calls = _count_pipelined(monkeypatch, gru_large.GRU)
     pipe = _run_gru(m, x, h0, g)
     assert calls, "the pipelined GRU stack did not run"
     set_tune(monkeypatch, large_pipe="0")
@@ -185,3 +195,38 @@ def test_layer_by_layer_overlap_matches_serial(cell, monkeypatch):
     for _ in range(4):
         for a, b in zip(grads(), ref):
             assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("state", [False, True])
+@pytest.mark.parametrize("pipe", [True, False])
+@pytest.mark.parametrize("cell", ["lstm", "gru"])
+def test_single_step_matches_fp64(cell, pipe, state, monkeypatch):
+    """T = 1 through the pipelined stack (its chunks clamp to one) and layer
+    by layer: no step has a previous output, so each layer's dW_hh is the h0
+    pairing alone, or a zero fill without an initial state (then the
+    reference's is exactly zero too and _rel is 0 / eps)."""
+    from pytorch_distributed_rnn_amd.models.rnn import GRU
+    torch.manual_seed(11)
+    L, B, T, I, H = 2, 5, 1, 9, 128
+    m = (LSTM if cell == "lstm" else GRU)(I, H, L, batch_first=True).cuda()
+    ref_m = (torch.nn.LSTM if cell == "lstm" else torch.nn.GRU)(I, H, L, batch_first=True).double().cuda()
+    with torch.no_grad():
+        for (_, p), (_, q) in zip(m.named_parameters(), ref_m.named_parameters()):
+            q.copy_(p.double())
+    x = torch.randn(B, T, I, device="cuda")
+    h0 = torch.randn(L, B, H, device="cuda") if state else None
+    c0 = torch.randn(L, B, H, device="cuda") if state else None
+    g = torch.randn(B, T, H, device="cuda")
+    if not pipe:
+        set_tune(monkeypatch, large_pipe="0")
+    calls = _count_pipelined(monkeypatch, lstm_large.LSTM if cell == "lstm" else gru_large.GRU)
+    if cell == "lstm":
+        got = _run(m, x, h0, c0, g)
+        ref = _run(ref_m, x.double(), h0.double() if state else None, c0.double() if state else None, g.double())
+    else:
+        got = _run_gru(m, x, h0, g)
+        ref = _run_gru(ref_m, x.double(), h0.double() if state else None, g.double())
+    assert len(calls) == (1 if pipe else 0)
+    assert set(got) == set(ref)
+    for k in got:
+        assert _rel(got[k], ref[k]) < 1e-4, k
