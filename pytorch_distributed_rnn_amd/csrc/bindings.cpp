@@ -1782,6 +1782,74 @@ Tensor gemm_nt(const Tensor& A, const Tensor& Bt, int64_t tile) {
                                  (int)tile, cur_stream()));
   return C;
 }
+
+// Char-LM generation (kernels/lstm_decode.hip): n_tokens positions of the
+// decode kernels, enqueued here in one go.  The buffers are the caller's (ops/decode.py).
+void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
+                 const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
+                 const Tensor& c, const Tensor& scratch, const Tensor& first, const optional<Tensor>& forced,
+                 const Tensor& tokens, const optional<Tensor>& logits, double temperature, int64_t seed,
+                 int64_t stream0, int64_t pos0) {
+  CHECK_HIP_TENSOR(emb);
+  const c10::DeviceGuard guard(emb.device());
+  const int dt = dtype_code(emb);
+  const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
+  TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
+              "lstm_decode: emb [V, E], one w_ih / w_hh / bias per layer");
+  TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
+              "lstm_decode: h [2, L, B, H] in the weights' dtype");
+  const int64_t B = h.size(2), H = h.size(3), N = tokens.dim() == 2 ? tokens.size(1) : 0;
+  TORCH_CHECK(pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
+              "lstm_decode: unsupported shape B=", B, " H=", H, " E=", E, " V=", V, " L=", L, " N=", N);
+  auto aligned = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  auto f32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
+  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
+  std::vector<const void*> pi(L), ph(L);
+  std::vector<const float*> pb(L);
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t I = l == 0 ? E : H;
+    TORCH_CHECK(w_ih[l].is_cuda() && w_ih[l].is_contiguous() && dtype_code(w_ih[l]) == dt && w_ih[l].dim() == 2 &&
+                w_ih[l].size(0) == 4 * H && w_ih[l].size(1) == I && aligned(w_ih[l]), "lstm_decode: w_ih [4H, I]");
+    TORCH_CHECK(w_hh[l].is_cuda() && w_hh[l].is_contiguous() && dtype_code(w_hh[l]) == dt && w_hh[l].dim() == 2 &&
+                w_hh[l].size(0) == 4 * H && w_hh[l].size(1) == H && aligned(w_hh[l]), "lstm_decode: w_hh [4H, H]");
+    TORCH_CHECK(f32(bias[l]) && bias[l].numel() == 4 * H, "lstm_decode: bias [4H] fp32");
+    pi[l] = w_ih[l].data_ptr();
+    ph[l] = w_hh[l].data_ptr();
+    pb[l] = bias[l].data_ptr<float>();
+  }
+  TORCH_CHECK(w_fc.is_cuda() && w_fc.is_contiguous() && dtype_code(w_fc) == dt && w_fc.dim() == 2 && w_fc.size(0) == V &&
+              w_fc.size(1) == H && aligned(w_fc) && aligned(emb) && aligned(h), "lstm_decode: w_fc [V, H]");
+  if (present(b_fc)) TORCH_CHECK(f32(*b_fc) && b_fc->numel() == V, "lstm_decode: b_fc [V] fp32");
+  TORCH_CHECK(f32(c) && c.numel() == L * B * H, "lstm_decode: c [L, B, H] fp32");
+  TORCH_CHECK(f32(scratch) && scratch.numel() == B * V, "lstm_decode: scratch [B, V] fp32");
+  TORCH_CHECK(i64(first) && first.numel() == B, "lstm_decode: first [B] int64");
+  TORCH_CHECK(i64(tokens) && tokens.size(0) == B, "lstm_decode: tokens [B, N] int64");
+  if (present(forced)) TORCH_CHECK(i64(*forced) && forced->dim() == 2 && forced->size(0) == B && forced->size(1) == N,
+                                   "lstm_decode: forced [B, N] int64");
+  if (present(logits)) TORCH_CHECK(f32(*logits) && logits->numel() == B * N * V, "lstm_decode: logits [B, N, V] fp32");
+  TORCH_CHECK(temperature >= 0.0, "lstm_decode: temperature >= 0");
+  PdrnnLstmDecodeArgs a{};
+  a.emb = emb.data_ptr();
+  a.w_ih = pi.data();
+  a.w_hh = ph.data();
+  a.bias = pb.data();
+  a.w_fc = w_fc.data_ptr();
+  a.b_fc = opt_ptr(b_fc);
+  a.h = h.data_ptr();
+  a.c = c.data_ptr<float>();
+  a.scratch = scratch.data_ptr<float>();
+  a.first = first.data_ptr<int64_t>();
+  a.forced = present(forced) ? forced->data_ptr<int64_t>() : nullptr;
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.logits = present(logits) ? logits->data_ptr<float>() : nullptr;
+  a.B = (int)B; a.H = (int)H; a.E = (int)E; a.V = (int)V; a.L = (int)L;
+  a.dtype = dt;
+  a.temperature = (float)temperature;
+  a.seed = (uint32_t)seed;
+  a.stream0 = (uint32_t)stream0;
+  a.pos0 = (uint32_t)pos0;
+  HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
+}
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1936,6 +2004,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "128x128 slices instead of 32x32, ping-pong GEMM + cell pair");
   m.def("lstm_large_bwd", &lstm_large_bwd, "large-H LSTM layer BPTT (MFMA step kernels) -> dgates, dh0, dc0");
   m.def("lstm_large_supported", [](int64_t H) { return pdrnn_lstm_large_supported((int)H) != 0; });
+  m.def("lstm_decode", &lstm_decode, "char-LM generation: n_tokens positions of the fused decode kernels",
+        py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
+        py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("forced"), py::arg("tokens"),
+        py::arg("logits"), py::arg("temperature"), py::arg("seed"), py::arg("stream0"), py::arg("pos0"));
+  m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
+    return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
+  }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
   m.def("lstm_rows_range_supported", [](int64_t H) { return rows_f32_on() && pdrnn_lstm_rows_f32_supported((int)H, 2) != 0; });
   m.def("lstm_rows_fwd_range", &lstm_rows_fwd_range, "row-owning fp32 recurrence over steps [t0, t1) (preallocated outputs)");
   m.def("lstm_rows_bwd_range", &lstm_rows_bwd_range, "row-owning fp32 BPTT over steps [t0, t1), last range first");

@@ -479,6 +479,39 @@ hipError_t pdrnn_slab_reduce_adam(const PdrnnAdamArgs* a, const float* A, int64_
                                   float* grad_out, float* tail_out, const float* slot_step, int slot_offset,
                                   int ring_rows, hipStream_t stream);
 
+// ---- char-LM generation (kernels/lstm_decode.hip) --------------------------
+// One token of a unidirectional 16-bit LSTM stack with biases for B <= 16
+// streams is L launches of the decode layer kernel plus one of the vocabulary
+// head; position p's input token is forced[b, p] if forced is given, else
+// first[b] at p = 0, else the token sampled from position p - 1's logits
+// (pdrnn/decode_rng.h; temperature 0: their argmax).  tokens[b, p] always
+// receives the token sampled from position p's logits.  The hash sees stream
+// stream0 + b and position pos0 + p.
+typedef struct {
+  const void* emb;           // [V, E] embedding, 16-bit
+  const void* const* w_ih;   // host array [L]: [4H, E] (layer 0) / [4H, H], gate-interleaved rows 4u + q, 16-bit
+  const void* const* w_hh;   // host array [L]: [4H, H], likewise
+  const float* const* bias;  // host array [L]: [4H] b_ih + b_hh, interleaved
+  const void* w_fc;          // [V, H] 16-bit
+  const float* b_fc;         // [V] or NULL
+  void* h;                   // [2, L, B, H] 16-bit: h entering position p in slot p & 1, leaving it in the other
+  float* c;                  // [L, B, H], updated in place
+  float* scratch;            // [B, V] the latest position's logits
+  const int64_t* first;      // [B]
+  const int64_t* forced;     // [B, n_tokens] or NULL
+  int64_t* tokens;           // [B, n_tokens]
+  float* logits;             // [B, n_tokens, V] or NULL
+  int B, H, E, V, L;
+  int dtype;                 // 0 bf16, 1 fp16
+  float temperature;
+  uint32_t seed, stream0, pos0;
+} PdrnnLstmDecodeArgs;
+// B <= 16, H % 64 == 0, E % 32 == 0, V <= 1024, 16-bit storage
+int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype);
+// Enqueues (L + 1) * n_tokens launches and a last sampling-only one; no host
+// read.  Every 16-bit pointer 16-byte aligned.
+hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
+
 // Diagnostics: a single wave that spins for `microseconds` (bounded, <= 60 s).
 // Communicator-watchdog tests only.
 hipError_t pdrnn_debug_spin(uint64_t microseconds, hipStream_t stream);

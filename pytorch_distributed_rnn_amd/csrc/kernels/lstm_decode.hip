@@ -1,0 +1,290 @@
+// Char-LM generation: one LSTM layer for ONE token and up to 16 streams per
+// launch, the vocabulary head, and the Gumbel-max sampler, for gfx950.
+//
+// Decoding a token is a chain of matrix-vector products: the work is streaming
+// the weights (about 28 MB at 2 x 1024, resident in the Infinity Cache), and
+// the training kernels' 256-row tiles and per-step host work are all overhead.
+// Here a token is L + 1 short launches on one stream and nothing else:
+//   * lstm_decode_layer<DT, FIRST>: [x_t | h_{t-1}] [W_ih | W_hh]^T on
+//     v_mfma_f32_16x16x32 with the WEIGHTS as the A operand and the streams,
+//     padded to 16, as B.  A workgroup owns 16 gate-interleaved rows (4 hidden
+//     units); its 8 waves split K and reduce through LDS.  In the accumulator
+//     layout a lane then holds rows 4(lane >> 4) + {0, 1, 2, 3} = gates i, f,
+//     g, o of one unit for stream lane & 15: the cell runs on a lane's own
+//     four registers, no exchange.  Padding streams are zero operands and are
+//     never stored.
+//   * FIRST (layer 0) first picks each stream's input token -- forced, the
+//     prompt's last, or sampled from the previous position's logits -- and
+//     reads x_t straight from that row of the 16-bit embedding.  Every
+//     workgroup samples the same B tokens on its own (B x V values, an argmax);
+//     workgroup 0 alone records them.
+//   * lstm_decode_head<DT>: logits = h_top W_fc^T + b_fc in fp32, 16
+//     vocabulary rows per workgroup, rows past V masked.
+// h ping-pongs between two buffers by token parity (every workgroup reads all
+// of h_{t-1} while the others write h_t); layer l > 0 reads layer l - 1's h_t
+// of the same token.  All ordering is kernel boundaries on one stream: nothing
+// inside a launch waits for another workgroup.
+//
+// Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) +
+// nn.Linear stepped one token at a time.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pdrnn/api.h"
+#include "pdrnn/common.h"
+#include "pdrnn/decode_rng.h"
+
+namespace pdrnn {
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct BF16 {
+  static __device__ __forceinline__ uint16_t from_f(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
+  static __device__ __forceinline__ f32x4 mfma(const uint4& a, const uint4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
+                                                   c, 0, 0, 0);
+  }
+};
+struct F16 {
+  static __device__ __forceinline__ uint16_t from_f(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+  static __device__ __forceinline__ f32x4 mfma(const uint4& a, const uint4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b),
+                                                  c, 0, 0, 0);
+  }
+};
+
+constexpr int kWaves = 8;               // K-split waves of a workgroup
+constexpr int kThreads = kWaves * kWave;
+constexpr int kStreams = 16;            // the MFMA tile's N side
+
+// What the sampler reads and writes (shared by layer 0 and the final launch).
+struct SampleArgs {
+  const float* scratch;   // [B, V] logits of the previous position
+  int64_t* tokens;        // [B, N]
+  int B, V, N;
+  float temperature;      // 0: greedy
+  uint32_t seed, stream0, pos0;
+};
+
+// tok[b] = argmax_v(logit / T + g), the lowest index on ties, for every stream
+// b < B; position p of the N generated ones (hash position pos0 + p).  Wave w
+// takes streams w, w + 8, ...; all lanes of the workgroup must call.
+__device__ __forceinline__ void sample_tokens(const SampleArgs& s, int p, int* tok) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int b = wave; b < s.B; b += kWaves) {
+    const uint32_t key = decode_key(s.seed, s.stream0 + (uint32_t)b, s.pos0 + (uint32_t)p);
+    const float* row = s.scratch + (int64_t)b * s.V;
+    float best = -INFINITY;
+    int bi = s.V;
+    for (int v = lane; v < s.V; v += kWave) {
+      float val = row[v];
+      if (s.temperature != 0.f) {
+        const float u = decode_uniform(decode_word(key, (uint32_t)v));
+        val = val / s.temperature + -logf(-logf(u));
+      }
+      if (val > best) { best = val; bi = v; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) tok[b] = bi < s.V ? bi : 0;  // (all-NaN logits: a valid row all the same)
+  }
+}
+
+struct LayerArgs {
+  const uint16_t* wx;     // [4H, Kx] gate-interleaved rows 4u + q
+  const uint16_t* wh;     // [4H, H]
+  const float* bias;      // [4H] b_ih + b_hh, interleaved
+  const uint16_t* x;      // FIRST: the embedding [V, Kx]; else the layer below's h_t [B, Kx]
+  const uint16_t* hprev;  // [B, H]
+  uint16_t* hout;         // [B, H]
+  float* c;               // [B, H], updated in place
+  const int64_t* first;   // FIRST: [B] input tokens of position 0
+  const int64_t* forced;  // FIRST: [B, N] input tokens of every position, or null
+  SampleArgs s;
+  int H, Kx, p;
+};
+
+// Sum of the waves' partial accumulators, in wave order, into wave 0.
+__device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  red[wave][lane] = acc;
+  __syncthreads();
+  f32x4 sum = red[0][lane];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) sum += red[w][lane];
+  return sum;
+}
+
+template <class DT, bool FIRST>
+__global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a) {
+  __shared__ f32x4 red[kWaves][kWave];
+  __shared__ int tok[kStreams];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, kq = lane >> 4;
+  const int B = a.s.B, H = a.H, Kx = a.Kx;
+  const bool live = n < B;
+
+  const uint16_t* xrow = a.x + (int64_t)n * Kx;  // (read only where live)
+  if constexpr (FIRST) {
+    // the sampled token is needed as an input only when nothing is forced;
+    // forced runs still record it, which is workgroup 0's job alone
+    const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
+    if (sample) sample_tokens(a.s, a.p - 1, tok);
+    __syncthreads();
+    if (sample && blockIdx.x == 0 && threadIdx.x < B)
+      a.s.tokens[(int64_t)threadIdx.x * a.s.N + a.p - 1] = tok[threadIdx.x];
+    int64_t t = 0;
+    if (live) {
+      if (a.forced != nullptr) t = a.forced[(int64_t)n * a.s.N + a.p];
+      else if (a.p == 0) t = a.first[n];
+      else t = tok[n];
+      PDRNN_DEVICE_ASSERT(t >= 0 && t < a.s.V);
+      t = t < 0 ? 0 : (t >= a.s.V ? a.s.V - 1 : t);  // a token outside the vocabulary reads no memory outside it
+    }
+    xrow = a.x + t * Kx;
+  }
+
+  // K blocks of 32: [0, Kx / 32) from x and W_ih, the rest from h_{t-1} and
+  // W_hh; wave w takes blocks w, w + 8, ...  Lane: weight row lane & 15 (A),
+  // stream lane & 15 (B), k = 8 (lane >> 4) + 0..7 of the block in both.
+  const int row = blockIdx.x * 16 + n;  // < 4H: the grid is H / 4
+  const uint16_t* wxr = a.wx + (int64_t)row * Kx + kq * 8;
+  const uint16_t* whr = a.wh + (int64_t)row * H + kq * 8;
+  const uint16_t* xr = xrow + kq * 8;
+  const uint16_t* hr = a.hprev + (int64_t)n * H + kq * 8;
+  const int nkx = Kx / 32, nkb = nkx + H / 32;
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int kb = wave; kb < nkb; kb += kWaves) {
+    const bool inx = kb < nkx;
+    const int k = (inx ? kb : kb - nkx) * 32;
+    const uint4 w = *reinterpret_cast<const uint4*>((inx ? wxr : whr) + k);
+    const uint4 v = live ? *reinterpret_cast<const uint4*>((inx ? xr : hr) + k) : zero;
+    acc = DT::mfma(w, v, acc);
+  }
+  const f32x4 z = reduce_waves(acc, red);
+  if (wave != 0 || !live) return;
+
+  // lane: unit 4 blockIdx + (lane >> 4), stream n; z[q] is gate q of it
+  const int u = blockIdx.x * 4 + kq;
+  const float* bs = a.bias + 4 * u;
+  const float gi = sigmoidf_fast(z[0] + bs[0]);
+  const float gf = sigmoidf_fast(z[1] + bs[1]);
+  const float gg = tanhf_fast(z[2] + bs[2]);
+  const float go = sigmoidf_fast(z[3] + bs[3]);
+  const int64_t at = (int64_t)n * H + u;
+  const float cn = fmaf(gf, a.c[at], gi * gg);
+  a.c[at] = cn;
+  a.hout[at] = DT::from_f(go * tanhf_fast(cn));
+}
+
+struct HeadArgs {
+  const uint16_t* w;   // [V, H]
+  const float* bias;   // [V] or null
+  const uint16_t* h;   // [B, H] the top layer's h_t
+  float* scratch;      // [B, V]
+  float* logits;       // [B, N, V] or null
+  int B, H, V, N, p;
+};
+
+template <class DT>
+__global__ __launch_bounds__(kThreads) void lstm_decode_head(const HeadArgs a) {
+  __shared__ f32x4 red[kWaves][kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, kq = lane >> 4;
+  const int H = a.H;
+  const bool live = n < a.B;
+  const int row = blockIdx.x * 16 + n;  // vocabulary row of the A operand; the tail rows are zero operands
+  const bool rowok = row < a.V;
+  const uint16_t* wr = a.w + (int64_t)row * H + kq * 8;
+  const uint16_t* hr = a.h + (int64_t)n * H + kq * 8;
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int kb = wave; kb < H / 32; kb += kWaves) {
+    const uint4 w = rowok ? *reinterpret_cast<const uint4*>(wr + kb * 32) : zero;
+    const uint4 v = live ? *reinterpret_cast<const uint4*>(hr + kb * 32) : zero;
+    acc = DT::mfma(w, v, acc);
+  }
+  const f32x4 z = reduce_waves(acc, red);
+  if (wave != 0 || !live) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int v = blockIdx.x * 16 + kq * 4 + i;
+    if (v >= a.V) break;
+    const float y = z[i] + (a.bias != nullptr ? a.bias[v] : 0.f);
+    a.scratch[(int64_t)n * a.V + v] = y;
+    if (a.logits != nullptr) a.logits[((int64_t)n * a.N + a.p) * a.V + v] = y;
+  }
+}
+
+// The last token: sampled from the last position's logits, recorded, fed to nothing.
+__global__ __launch_bounds__(kThreads) void lstm_decode_sample(const SampleArgs s) {
+  __shared__ int tok[kStreams];
+  sample_tokens(s, s.N - 1, tok);
+  __syncthreads();
+  if (threadIdx.x < s.B) s.tokens[(int64_t)threadIdx.x * s.N + s.N - 1] = tok[threadIdx.x];
+}
+
+template <class DT>
+hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
+  const int B = a->B, H = a->H, E = a->E, V = a->V, L = a->L;
+  const SampleArgs s{a->scratch, a->tokens, B, V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0};
+  const uint16_t* h = static_cast<const uint16_t*>(a->h);
+  uint16_t* hm = static_cast<uint16_t*>(a->h);
+  const int64_t BH = (int64_t)B * H, slot = (int64_t)L * BH;
+  for (int p = 0; p < n_tokens; ++p) {
+    const int64_t in = (p & 1) * slot, out = ((p + 1) & 1) * slot;  // h_{t-1} and h_t of every layer
+    for (int l = 0; l < L; ++l) {
+      LayerArgs k{};
+      k.wx = static_cast<const uint16_t*>(a->w_ih[l]);
+      k.wh = static_cast<const uint16_t*>(a->w_hh[l]);
+      k.bias = a->bias[l];
+      k.x = l == 0 ? static_cast<const uint16_t*>(a->emb) : h + out + (l - 1) * BH;
+      k.hprev = h + in + l * BH;
+      k.hout = hm + out + l * BH;
+      k.c = a->c + l * BH;
+      k.first = a->first;
+      k.forced = a->forced;
+      k.s = s;
+      k.H = H;
+      k.Kx = l == 0 ? E : H;
+      k.p = p;
+      if (l == 0) lstm_decode_layer<DT, true><<<H / 4, kThreads, 0, stream>>>(k);
+      else lstm_decode_layer<DT, false><<<H / 4, kThreads, 0, stream>>>(k);
+      PDRNN_HIP_CHECK(hipGetLastError());
+    }
+    const HeadArgs hd{static_cast<const uint16_t*>(a->w_fc), a->b_fc, h + out + (L - 1) * BH, a->scratch, a->logits,
+                      B, H, V, n_tokens, p};
+    lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
+    PDRNN_HIP_CHECK(hipGetLastError());
+  }
+  lstm_decode_sample<<<1, kThreads, 0, stream>>>(s);
+  return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace pdrnn
+
+extern "C" {
+
+int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype) {
+  return B >= 1 && B <= pdrnn::kStreams && pdrnn_lstm_large_supported(H) && E >= 32 && E % 32 == 0 && V >= 1 &&
+         V <= 1024 && L >= 1 && (dtype == 0 || dtype == 1);
+}
+
+hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
+  if (n_tokens < 1 || !pdrnn_lstm_decode_supported(a->B, a->H, a->E, a->V, a->L, a->dtype)) return hipErrorInvalidValue;
+  if (!(a->temperature >= 0.f)) return hipErrorInvalidValue;
+  return a->dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
+}
+
+}  // extern "C"

@@ -1,12 +1,17 @@
-"""Char-LM training entry point (BASELINE config 4).
+"""Char-LM training and generation entry point (BASELINE config 4).
 
     python -m pytorch_distributed_rnn_amd.lm_cli --hidden 1024 --layers 2 --seq-len 512 \\
         --batch-size 64 --max-steps 100 local
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m pytorch_distributed_rnn_amd.lm_cli ... distributed
 
+    python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-epoch0.pt \\
+        --prompt "The " --num-tokens 256 --temperature 0.8 --samples 4 generate
+
 Data: ``--text FILE`` (bytes) or a synthetic corpus (default).  ``--batch-size``
-is global (strong scaling) unless ``--weak-scaling``.
+is global (strong scaling) unless ``--weak-scaling``.  ``generate`` rebuilds
+the model from the checkpoint alone (only ``--dtype`` is read from the command
+line) and samples ``--samples`` continuations of the prompt.
 """
 from __future__ import annotations
 
@@ -25,7 +30,7 @@ DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="char-LM LSTM training")
+    p = argparse.ArgumentParser(description="char-LM LSTM training and generation")
     p.add_argument("--text", default=None)
     p.add_argument("--synthetic-tokens", type=int, default=4_000_000)
     p.add_argument("--vocab", type=int, default=256)
@@ -52,13 +57,62 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resume", default=None, help="checkpoint to continue from")
     p.add_argument("--trace", action="store_true", help="roctx / torch.profiler ranges around step phases")
     p.add_argument("--profile", default=None, help="torch.profiler capture of the run into this directory")
-    p.add_argument("mode", choices=("local", "distributed"))
+    g = p.add_argument_group("generate")
+    g.add_argument("--checkpoint", default=None, help="the trained model to sample from (required)")
+    g.add_argument("--prompt", default=None, help="text the samples continue (UTF-8 bytes are the tokens)")
+    g.add_argument("--prompt-file", default=None, help="the prompt's bytes from a file instead")
+    g.add_argument("--num-tokens", type=int, default=256)
+    g.add_argument("--temperature", type=float, default=1.0, help="0: greedy")
+    g.add_argument("--samples", type=int, default=1)
+    g.add_argument("--output", default=None, help="write the samples' raw bytes here, one after another")
+    p.add_argument("mode", choices=("local", "distributed", "generate"))
     return p
+
+
+def generate(args):
+    """``generate``: rebuild the model a checkpoint describes and sample
+    ``--samples`` continuations of the prompt, ``--num-tokens`` tokens each.
+    The samples are the rows of one batch, so they differ by their row index
+    in the sampling hash; the same ``--seed`` gives the same text again."""
+    from .models.charlm import charlm_from_state_dict
+    from .train import checkpoint as ckpt
+    from .train.trainer import default_device
+    if not args.checkpoint:
+        raise SystemExit("generate: --checkpoint is required")
+    if args.prompt is not None and args.prompt_file is not None:
+        raise SystemExit("generate: give --prompt or --prompt-file, not both")
+    if args.samples < 1 or args.num_tokens < 0 or args.temperature < 0:
+        raise SystemExit("generate: --samples >= 1, --num-tokens >= 0 and --temperature >= 0")
+    if args.prompt_file is not None:
+        with open(args.prompt_file, "rb") as f:
+            prompt = f.read()
+    else:
+        prompt = (args.prompt if args.prompt is not None else "\n").encode("utf-8")
+    if not prompt:
+        raise SystemExit("generate: the prompt is empty")
+    model = charlm_from_state_dict(ckpt.read_checkpoint(args.checkpoint)["model_state"], DTYPES[args.dtype])
+    if model.vocab_size > 256:
+        raise SystemExit(f"generate: a vocabulary of {model.vocab_size} entries is not bytes")
+    if max(prompt) >= model.vocab_size:
+        raise SystemExit(f"generate: the prompt holds byte {max(prompt)}, the model's vocabulary is {model.vocab_size}")
+    device = torch.device(args.device) if args.device else default_device()
+    model = model.to(device).eval()
+    tokens = model.generate(torch.tensor(list(prompt), dtype=torch.int64).repeat(args.samples, 1), args.num_tokens,
+                            temperature=args.temperature, seed=args.seed)
+    samples = [bytes(row) for row in tokens.cpu().tolist()]  # (a 256-entry vocabulary at the most: bytes)
+    if args.output:
+        with open(args.output, "wb") as f:
+            f.write(b"".join(samples))
+    for s in samples:
+        print(s.decode("utf-8", errors="replace"))
+    return samples
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=args.log, format="%(message)s")
+    if args.mode == "generate":
+        return generate(args)
     torch.manual_seed(args.seed)
     corpus = (CharCorpus.from_text(args.text) if args.text
               else CharCorpus.synthetic(args.synthetic_tokens, args.vocab, seed=args.seed))

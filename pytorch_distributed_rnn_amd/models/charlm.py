@@ -60,6 +60,104 @@ class CharLM(nn.Module):
             self._state = (hn.detach(), cn.detach())
         return linear(out, self.fc.weight, self.fc.bias)  # in-tree GEMM head (ops/gemm.py)
 
+    def _step(self, tokens: Tensor, state):
+        """One ``forward`` call from an explicit state -> (last position's
+        logits [B, V], new state), through the carry the training loop uses."""
+        self._state = state
+        logits = self.forward(tokens, carry=True)
+        return logits[-1], self._state
+
+    @torch.no_grad()
+    def generate(self, prompt: Tensor, num_tokens: int, temperature: float = 1.0, seed: int = 0,
+                 state: Optional[Tuple[Tensor, Tensor]] = None, forced: Optional[Tensor] = None,
+                 return_logits: bool = False, return_state: bool = False):
+        """Sample ``num_tokens`` tokens after ``prompt`` [B, P] (P >= 1) ->
+        tokens [B, num_tokens] int64 (, logits [B, num_tokens, V] fp32)
+        (, (h, c) [layers, B, H], c in fp32 on the fused path).
+
+        The rule is ops/decode.py's: ``token = argmax(logits / temperature +
+        Gumbel noise)``, the noise a hash of (seed, row of the batch, position
+        counted from the prompt's start, vocabulary entry); temperature 0 is
+        greedy.  ``prompt[:, :-1]`` runs through ``forward`` from ``state``
+        (zeros when None); the last prompt token is the first input.
+        ``forced`` [B, num_tokens] replaces every position's input token (the
+        sampled ones are still returned): scoring a given continuation.
+
+        On the GPU, 16-bit models the decode kernels cover run on them
+        (kernels/lstm_decode.hip; more than 16 rows as independent groups of
+        16); everything else takes the reference path, ``forward`` one token at
+        a time -- an error under ``PDRNN_KERNELS=hip-strict``.  Dropout is off
+        and the truncated-BPTT carry is left as it was."""
+        from .. import _ext
+        from ..ops import decode as dec
+        if prompt.dim() != 2 or prompt.shape[1] < 1:
+            raise ValueError("generate: prompt must be [B, P] with P >= 1")
+        dev = self.embedding.weight.device
+        prompt = prompt.to(dev, torch.int64)
+        forced = forced.to(dev, torch.int64) if forced is not None else None
+        B, P = prompt.shape
+        N = int(num_tokens)
+        if forced is not None and tuple(forced.shape) != (B, N):
+            raise ValueError("generate: forced must be [B, num_tokens]")
+        for name, t in (("prompt", prompt), ("forced", forced)):
+            if t is not None and t.device.type == "cpu" and t.numel() and not (0 <= int(t.min()) and int(t.max()) < self.vocab_size):
+                raise ValueError(f"generate: {name} holds tokens outside the vocabulary")
+        V, E, H, L = self.vocab_size, self.embedding.embedding_dim, self.hidden_dim, self.num_layers
+        kept, training = self._state, self.training
+        self.eval()
+        try:
+            if P > 1:
+                _, state = self._step(prompt[:, :-1], state)
+            first = prompt[:, -1]
+            cdt = self._cdt(dev)
+            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+            if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev):
+                outs = []
+                for b0 in range(0, B, dec.MAX_STREAMS):
+                    rows = slice(b0, min(b0 + dec.MAX_STREAMS, B))
+                    outs.append(dec.decode(
+                        self.embedding.weight, self.lstm._weights(), self.fc.weight, self.fc.bias, cdt,
+                        state[0][:, rows] if state is not None else None, state[1][:, rows] if state is not None else None,
+                        first[rows], N, temperature=temperature, seed=seed, stream0=b0, pos0=P,
+                        forced=forced[rows] if forced is not None else None, return_logits=return_logits))
+                if len(outs) == 1:
+                    tokens, logits, h, c = outs[0]
+                else:
+                    tokens = torch.cat([o[0] for o in outs], 0)
+                    logits = torch.cat([o[1] for o in outs], 0) if return_logits else None
+                    h, c = torch.cat([o[2] for o in outs], 1), torch.cat([o[3] for o in outs], 1)
+                state = (h, c)
+            else:
+                if N > 0:
+                    _ext.fallback(f"char-LM decode (B={B}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
+                tokens, logits, state = dec.reference(self._step, state, first, N, temperature=temperature, seed=seed,
+                                                      pos0=P, forced=forced, return_logits=return_logits)
+                if return_logits and logits is None:  # (no position at all)
+                    logits = torch.empty(B, 0, V, device=dev)
+        finally:
+            self._state = kept
+            self.train(training)
+        out = (tokens,) + ((logits,) if return_logits else ()) + ((state,) if return_state else ())
+        return out[0] if len(out) == 1 else out
+
+
+def charlm_from_state_dict(state, compute_dtype: torch.dtype = torch.bfloat16) -> CharLM:
+    """A ``CharLM`` with the hyper-parameters a checkpoint's ``model_state``
+    implies, its parameters loaded: vocabulary and embedding width from
+    ``embedding.weight``, the hidden size from ``lstm.weight_hh_l0``, the
+    layers from the key count; DDP's ``module.`` prefix is accepted."""
+    from ..train.checkpoint import adapt_state_dict_keys
+    plain = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    for k in ("embedding.weight", "lstm.weight_hh_l0", "fc.weight"):
+        if k not in plain:
+            raise KeyError(f"not a char-LM state: {k} missing")
+    vocab, embed = (int(n) for n in plain["embedding.weight"].shape)
+    hidden = int(plain["lstm.weight_hh_l0"].shape[1])
+    layers = sum(1 for k in plain if k.startswith("lstm.weight_hh_l") and not k.endswith("_reverse"))
+    model = CharLM(vocab, embed, hidden, layers, compute_dtype=compute_dtype)
+    model.load_state_dict(adapt_state_dict_keys(dict(state), model))
+    return model
+
 
 class BiLSTMEncoder(nn.Module):
     """Stacked bidirectional LSTM with a per-timestep linear head."""
