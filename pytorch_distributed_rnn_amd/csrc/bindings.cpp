@@ -1850,6 +1850,54 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
   a.pos0 = (uint32_t)pos0;
   HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
 }
+
+// Char-LM evaluation (kernels/head_nll.hip): the vocabulary head, log-softmax,
+// NLL and argmax of h [N, H] (any row stride) in one kernel; accum [3] fp64 is
+// added to.  Returns (row_nll [N] fp32, pred [N] int32), the caller's buffers when given.
+std::tuple<Tensor, Tensor> head_nll(const Tensor& h, const Tensor& w, const optional<Tensor>& bias, const Tensor& labels,
+                                    int64_t ignore_index, const Tensor& accum, const optional<Tensor>& row_nll_out,
+                                    const optional<Tensor>& pred_out) {
+  CHECK_HIP_TENSOR(h);
+  const c10::DeviceGuard guard(h.device());
+  const int dt = dtype_code(h);
+  TORCH_CHECK(h.dim() == 2 && h.size(0) >= 1 && h.stride(1) == 1 && h.stride(0) >= h.size(1) && h.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
+              "head_nll: h [N, H], unit inner stride, rows a multiple of 8 elements apart, 16-byte aligned");
+  const int64_t N = h.size(0), H = h.size(1);
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && w.size(1) == H && dtype_code(w) == dt &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "head_nll: w [V, H] contiguous in h's dtype");
+  const int64_t V = w.size(0);
+  TORCH_CHECK(pdrnn_head_nll_supported((int)H, (int)V, dt), "head_nll: unsupported shape H=", H, " V=", V);
+  if (present(bias)) TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+                                 bias->numel() == V, "head_nll: bias [V] fp32");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == N,
+              "head_nll: labels [N] int64");
+  TORCH_CHECK(accum.is_cuda() && accum.scalar_type() == at::kDouble && accum.is_contiguous() && accum.numel() == 3,
+              "head_nll: accum [3] fp64");
+  if (present(row_nll_out)) TORCH_CHECK(row_nll_out->is_cuda() && row_nll_out->scalar_type() == at::kFloat &&
+                                        row_nll_out->is_contiguous() && row_nll_out->numel() == N, "head_nll: row_nll [N] fp32");
+  if (present(pred_out)) TORCH_CHECK(pred_out->is_cuda() && pred_out->scalar_type() == at::kInt && pred_out->is_contiguous() &&
+                                     pred_out->numel() == N, "head_nll: pred [N] int32");
+  Tensor row_nll = present(row_nll_out) ? *row_nll_out : at::empty({N}, h.options().dtype(at::kFloat));
+  Tensor pred = present(pred_out) ? *pred_out : at::empty({N}, h.options().dtype(at::kInt));
+  Tensor partial = at::empty({(int64_t)pdrnn_head_nll_blocks(N), 3}, h.options().dtype(at::kDouble));
+  PdrnnHeadNllArgs a{};
+  a.h = h.data_ptr();
+  a.ldh = h.stride(0);
+  a.w = w.data_ptr();
+  a.bias = opt_ptr(bias);
+  a.labels = labels.data_ptr<int64_t>();
+  a.N = N;
+  a.ignore_index = ignore_index;
+  a.row_nll = row_nll.data_ptr<float>();
+  a.pred = pred.data_ptr<int>();
+  a.partial = partial.data_ptr<double>();
+  a.accum = accum.data_ptr<double>();
+  a.H = (int)H; a.V = (int)V;
+  a.dtype = dt;
+  HIP_LAUNCH_CHECK(pdrnn_head_nll(&a, cur_stream()));
+  return std::make_tuple(row_nll, pred);
+}
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2011,6 +2059,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
     return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
   }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
+  m.def("head_nll", &head_nll, "fused vocabulary head + log-softmax + NLL + argmax -> (row_nll, pred); accum += sums",
+        py::arg("h"), py::arg("w16"), py::arg("bias"), py::arg("labels"), py::arg("ignore_index"), py::arg("accum"),
+        py::arg("row_nll") = py::none(), py::arg("pred") = py::none());
+  m.def("head_nll_supported", [](int64_t H, int64_t V, int64_t dtype) {
+    return H < (1LL << 31) && V < (1LL << 31) && pdrnn_head_nll_supported((int)H, (int)V, (int)dtype) != 0;
+  }, "the fused head/NLL kernel covers the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
   m.def("lstm_rows_range_supported", [](int64_t H) { return rows_f32_on() && pdrnn_lstm_rows_f32_supported((int)H, 2) != 0; });
   m.def("lstm_rows_fwd_range", &lstm_rows_fwd_range, "row-owning fp32 recurrence over steps [t0, t1) (preallocated outputs)");
   m.def("lstm_rows_bwd_range", &lstm_rows_bwd_range, "row-owning fp32 BPTT over steps [t0, t1), last range first");

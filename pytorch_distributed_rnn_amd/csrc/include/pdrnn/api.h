@@ -512,6 +512,33 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype);
 // read.  Every 16-bit pointer 16-byte aligned.
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
 
+// ---- char-LM evaluation (kernels/head_nll.hip) ------------------------------
+// Vocabulary head + log-softmax + NLL + argmax, the logits kept in fp32 MFMA
+// accumulators and never stored.  row_nll[r] = logsumexp(logits_r) -
+// logits_r[label_r], 0 for a row that is not valid (pdrnn_xent_fwd's terms:
+// label == ignore_index or outside [0, V)); pred[r] = the argmax, the lowest
+// index on ties, for every row; accum += [sum row_nll, n_valid, n_correct],
+// summed in fp64 in a fixed order by a second one-block launch.
+typedef struct {
+  const void* h;             // [N, H] 16-bit, row stride ldh elements (ldh % 8 == 0), 16-byte aligned
+  int64_t ldh;
+  const void* w;             // [V, H] 16-bit contiguous, 16-byte aligned
+  const float* bias;         // [V] or NULL
+  const int64_t* labels;     // [N]
+  int64_t N;
+  int64_t ignore_index;
+  float* row_nll;            // [N]
+  int* pred;                 // [N]
+  double* partial;           // [pdrnn_head_nll_blocks(N), 3] scratch
+  double* accum;             // [3], added to
+  int H, V;
+  int dtype;                 // 0 bf16, 1 fp16
+} PdrnnHeadNllArgs;
+// H % 32 == 0, 1 <= V <= 1024, 16-bit storage
+int pdrnn_head_nll_supported(int H, int V, int dtype);
+int pdrnn_head_nll_blocks(int64_t N);
+hipError_t pdrnn_head_nll(const PdrnnHeadNllArgs* a, hipStream_t stream);
+
 // Diagnostics: a single wave that spins for `microseconds` (bounded, <= 60 s).
 // Communicator-watchdog tests only.
 hipError_t pdrnn_debug_spin(uint64_t microseconds, hipStream_t stream);

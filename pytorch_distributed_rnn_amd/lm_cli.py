@@ -1,4 +1,4 @@
-"""Char-LM training and generation entry point (BASELINE config 4).
+"""Char-LM training, evaluation and generation entry point (BASELINE config 4).
 
     python -m pytorch_distributed_rnn_amd.lm_cli --hidden 1024 --layers 2 --seq-len 512 \\
         --batch-size 64 --max-steps 100 local
@@ -8,10 +8,20 @@
     python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-epoch0.pt \\
         --prompt "The " --num-tokens 256 --temperature 0.8 --samples 4 generate
 
+    python -m pytorch_distributed_rnn_amd.lm_cli --text corpus.txt --validation-fraction 0.1 \\
+        --checkpoint-directory out local
+    python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-best.pt --text test.txt evaluate
+
 Data: ``--text FILE`` (bytes) or a synthetic corpus (default).  ``--batch-size``
-is global (strong scaling) unless ``--weak-scaling``.  ``generate`` rebuilds
-the model from the checkpoint alone (only ``--dtype`` is read from the command
-line) and samples ``--samples`` continuations of the prompt.
+is global (strong scaling) unless ``--weak-scaling``.  ``--validation-fraction
+F`` holds the last F of the token stream out of training: every epoch then
+ends with its loss, bits per character and accuracy (``val_*`` in the
+history), and ``charlm-best.pt`` keeps the checkpoint with the lowest
+``val_loss``.  ``generate`` and ``evaluate`` rebuild the model from the
+checkpoint alone (only ``--dtype`` is read from the command line); ``generate``
+samples ``--samples`` continuations of the prompt, ``evaluate`` scores
+``--text`` or the synthetic corpus (with ``--validation-fraction`` its held-out
+tail only: a training run's validation figure again, from its checkpoint).
 """
 from __future__ import annotations
 
@@ -19,6 +29,7 @@ import argparse
 import json
 import logging
 import sys
+from typing import Optional
 
 import torch
 
@@ -57,16 +68,35 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resume", default=None, help="checkpoint to continue from")
     p.add_argument("--trace", action="store_true", help="roctx / torch.profiler ranges around step phases")
     p.add_argument("--profile", default=None, help="torch.profiler capture of the run into this directory")
-    g = p.add_argument_group("generate")
-    g.add_argument("--checkpoint", default=None, help="the trained model to sample from (required)")
+    p.add_argument("--validation-fraction", type=float, default=0.0,
+                   help="hold the last F of the token stream out of training and evaluate it after every epoch")
+    p.add_argument("--eval-batch-size", type=int, default=16, help="parallel streams of an evaluation")
+    g = p.add_argument_group("generate / evaluate")
+    g.add_argument("--checkpoint", default=None, help="the trained model to sample from or to score with (required)")
     g.add_argument("--prompt", default=None, help="text the samples continue (UTF-8 bytes are the tokens)")
     g.add_argument("--prompt-file", default=None, help="the prompt's bytes from a file instead")
     g.add_argument("--num-tokens", type=int, default=256)
     g.add_argument("--temperature", type=float, default=1.0, help="0: greedy")
     g.add_argument("--samples", type=int, default=1)
-    g.add_argument("--output", default=None, help="write the samples' raw bytes here, one after another")
-    p.add_argument("mode", choices=("local", "distributed", "generate"))
+    g.add_argument("--output", default=None, help="generate: write the samples' raw bytes here, one after another; "
+                                                   "evaluate: write the figures here as JSON")
+    p.add_argument("mode", choices=("local", "distributed", "generate", "evaluate"))
     return p
+
+
+def load_corpus(args) -> CharCorpus:
+    return (CharCorpus.from_text(args.text) if args.text
+            else CharCorpus.synthetic(args.synthetic_tokens, args.vocab, seed=args.seed))
+
+
+def split_corpus(corpus: CharCorpus, fraction: float):
+    """(training part, held-out part or None): the last ``fraction`` of the
+    token stream is held out; at 0 the training part is the corpus itself."""
+    if fraction == 0:
+        return corpus, None
+    n_val = int(len(corpus) * fraction)
+    cut = len(corpus) - n_val
+    return CharCorpus(corpus.tokens[:cut], corpus.vocab_size), CharCorpus(corpus.tokens[cut:], corpus.vocab_size)
 
 
 def generate(args):
@@ -108,22 +138,70 @@ def generate(args):
     return samples
 
 
+def _check_split(args, mode: str, corpus: CharCorpus, held: Optional[CharCorpus]) -> None:
+    if not 0 <= args.validation_fraction < 1:
+        raise SystemExit(f"{mode}: --validation-fraction must be in [0, 1)")
+    if args.eval_batch_size < 1:
+        raise SystemExit(f"{mode}: --eval-batch-size >= 1")
+    if held is not None and len(held) < 2 * args.eval_batch_size:
+        raise SystemExit(f"{mode}: the held-out part has {len(held)} tokens, too few for {args.eval_batch_size} streams")
+    if len(corpus) < 2:
+        raise SystemExit(f"{mode}: the corpus has {len(corpus)} tokens")
+
+
+def evaluate(args):
+    """``evaluate``: rebuild the model a checkpoint describes and score a text
+    with it: loss (nats per token), bits per character and next-token accuracy
+    over ``--eval-batch-size`` parallel streams of ``--seq-len`` windows, the
+    state carried from window to window."""
+    from .models.charlm import charlm_from_state_dict
+    from .train import checkpoint as ckpt
+    from .train.trainer import default_device
+    if not args.checkpoint:
+        raise SystemExit("evaluate: --checkpoint is required")
+    if args.seq_len < 1:
+        raise SystemExit("evaluate: --seq-len >= 1")
+    if not 0 <= args.validation_fraction < 1:
+        raise SystemExit("evaluate: --validation-fraction must be in [0, 1)")
+    corpus, held = split_corpus(load_corpus(args), args.validation_fraction)
+    _check_split(args, "evaluate", corpus, held)
+    scored = held if held is not None else corpus
+    if len(scored) < 2 * args.eval_batch_size:
+        raise SystemExit(f"evaluate: {len(scored)} tokens are too few for {args.eval_batch_size} streams")
+    model = charlm_from_state_dict(ckpt.read_checkpoint(args.checkpoint)["model_state"], DTYPES[args.dtype])
+    if int(scored.tokens.max()) >= model.vocab_size:
+        raise SystemExit(f"evaluate: the text holds token {int(scored.tokens.max())}, the model's vocabulary is "
+                         f"{model.vocab_size}")
+    device = torch.device(args.device) if args.device else default_device()
+    trainer = LMTrainer(model, scored, args.eval_batch_size, args.seq_len, device=device)
+    out = trainer.evaluate(scored, args.eval_batch_size, args.seq_len)
+    print(f"loss {out['loss']:.6f} bpc {out['bpc']:.4f} accuracy {out['accuracy']:.4f} tokens {out['tokens']}")
+    if args.output:
+        with open(args.output, "w") as f:
+            json.dump(out, f)
+    return out
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=args.log, format="%(message)s")
     if args.mode == "generate":
         return generate(args)
+    if args.mode == "evaluate":
+        return evaluate(args)
     torch.manual_seed(args.seed)
-    corpus = (CharCorpus.from_text(args.text) if args.text
-              else CharCorpus.synthetic(args.synthetic_tokens, args.vocab, seed=args.seed))
+    corpus, held = split_corpus(load_corpus(args), args.validation_fraction)
+    _check_split(args, args.mode, corpus, held)
     model = CharLM(corpus.vocab_size, args.embed, args.hidden, args.layers, args.dropout, DTYPES[args.dtype])
     device = torch.device(args.device) if args.device else None
     trainer = LMTrainer(model, corpus, args.batch_size, args.seq_len, args.learning_rate, device=device,
                         distributed=args.mode == "distributed", backend=args.backend,
                         grad_clip=args.grad_clip, log_interval=args.log_interval,
-                        bucket_cap_mb=args.bucket_mb, weak_scaling=args.weak_scaling)
+                        bucket_cap_mb=args.bucket_mb, weak_scaling=args.weak_scaling,
+                        validation=held, eval_batch=args.eval_batch_size)
     start = trainer.resume(args.resume) if args.resume else 0
     history = []
+    best = float("inf")
     from .utils import tracing
     if args.trace:
         tracing.enable(True)
@@ -134,6 +212,9 @@ def main(argv=None):
             if args.checkpoint_directory:
                 from pathlib import Path
                 trainer.save(Path(args.checkpoint_directory) / f"charlm-epoch{e}.pt", e, h["loss"])
+                if "val_loss" in h and h["val_loss"] < best:  # (rank 0 alone evaluates)
+                    best = h["val_loss"]
+                    trainer.save(Path(args.checkpoint_directory) / "charlm-best.pt", e, h["loss"])
     if trainer.rank == 0 and args.history_file:
         with open(args.history_file, "w") as f:
             json.dump(history, f)

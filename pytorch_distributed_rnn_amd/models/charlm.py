@@ -141,6 +141,41 @@ class CharLM(nn.Module):
         return out[0] if len(out) == 1 else out
 
 
+    @torch.no_grad()
+    def score(self, inputs: Tensor, targets: Tensor, state: Optional[Tuple[Tensor, Tensor]] = None,
+              return_state: bool = False, ignore_index: int = -100, accum: Optional[Tensor] = None):
+        """Per-token log-probabilities of ``targets`` [B, T] after ``inputs``
+        [B, T] -> (logprob [B, T] fp32, pred [B, T] int32) (, (h, c) [layers,
+        B, H]); ``logprob`` is 0 where the target is ``ignore_index``, ``pred``
+        the argmax of the position's logits (the lowest index on ties).
+
+        The embedding and the LSTM stack run as in ``forward`` from ``state``
+        (zeros when None); the vocabulary head, the log-softmax and the NLL are
+        one kernel on the top layer's output in place (ops/head_nll.py), with
+        the logits in fp32 from the product to the loss -- ``forward`` would
+        round them to the compute dtype first.  ``accum`` (fp64 [3], added to:
+        sum of -logprob, valid tokens, correct predictions) lets a caller total
+        many windows on the device.  Dropout is off; the training mode and the
+        truncated-BPTT carry are left as they were."""
+        from ..ops.head_nll import head_nll
+        if inputs.dim() != 2 or inputs.shape != targets.shape:
+            raise ValueError("score: inputs and targets must both be [B, T]")
+        dev = self.embedding.weight.device
+        inputs, targets = inputs.to(dev, torch.int64), targets.to(dev, torch.int64)
+        B, T = inputs.shape
+        training = self.training
+        self.eval()
+        try:
+            x = embedding(inputs.t(), self.embedding.weight, out_dtype=self._cdt(dev))  # [T, B, E]
+            out, (hn, cn) = self.lstm(x, state)                                          # [T, B, H]
+            row_nll, pred, _ = head_nll(out, self.fc.weight, self.fc.bias, targets.t().contiguous(), ignore_index, accum)
+        finally:
+            self.train(training)
+        logprob = -row_nll.view(T, B).t()
+        pred = pred.view(T, B).t()
+        return (logprob, pred, (hn, cn)) if return_state else (logprob, pred)
+
+
 def charlm_from_state_dict(state, compute_dtype: torch.dtype = torch.bfloat16) -> CharLM:
     """A ``CharLM`` with the hyper-parameters a checkpoint's ``model_state``
     implies, its parameters loaded: vocabulary and embedding width from

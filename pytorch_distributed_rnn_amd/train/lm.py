@@ -35,7 +35,8 @@ class LMTrainer:
                  learning_rate: float = 2e-3, device: Optional[torch.device] = None,
                  distributed: bool = False, backend: Optional[str] = None, grad_clip: float = 1.0,
                  log_interval: int = 50, bucket_cap_mb: Optional[float] = None,
-                 weak_scaling: bool = False, force_ddp: bool = False):
+                 weak_scaling: bool = False, force_ddp: bool = False,
+                 validation: Optional[CharCorpus] = None, eval_batch: int = 16):
         self.rank, self.world = 0, 1
         if distributed:
             info = env.init_distributed(backend)
@@ -68,6 +69,10 @@ class LMTrainer:
         self.global_batch = gb
         self.streams = corpus.streams(gb, self.rank, self.world).to(device)
         self.vocab = corpus.vocab_size
+        # held-out tokens: every epoch ends with an evaluation of them, on rank 0
+        # alone (as the motion DistributedTrainer keeps its validation set)
+        self.validation = validation if self.rank == 0 else None
+        self.eval_batch = eval_batch
         self._pending: List[dict] = []  # steps not yet verified (deferred verification)
         self.direct_grads = True  # one process: gradients written into the flat views (see _fwd_bwd)
 
@@ -215,7 +220,60 @@ class LMTrainer:
         logging.info(f"{self.rank}: Epoch {epoch} loss {mean:.6f} tokens/s {out['tokens_per_sec']:.1f} "
                      f"(x{self.world} ranks) device_peak_mib={out['device_peak_mib']:.1f} "
                      f"persist_verify={ps['persist_verify']} persist_fallbacks={ps['persist_fallbacks']}")
+        if self.validation is not None:
+            ev = self.evaluate(self.validation, self.eval_batch)
+            out.update(val_loss=ev["loss"], val_bpc=ev["bpc"], val_accuracy=ev["accuracy"])
+            logging.info(f"{self.rank}: Epoch {epoch} val_loss {ev['loss']:.6f} val_bpc {ev['bpc']:.4f} "
+                         f"val_accuracy {ev['accuracy']:.4f} ({ev['tokens']} tokens, {ev['tokens_per_sec']:.1f} tokens/s)")
         return out
+
+    # ------------------------------------------------------------- evaluation
+    def _score_streams(self, streams: Tensor, seq_len: int) -> Tensor:
+        """[sum nll, tokens, correct] (fp64, on the device) of every target of
+        ``streams`` [B, L], window by window with the state carried."""
+        from ..ops.head_nll import new_accum
+        accum = new_accum(self.device)
+        state = None
+        windows = 0
+        for inp, tgt in CharCorpus.segments(streams, seq_len):
+            _, _, state = self.inner.score(inp, tgt, state=state, return_state=True, accum=accum)
+            windows += 1
+        rest = (streams.shape[1] - 1) - windows * seq_len  # the tail shorter than a window is scored too
+        if rest > 0:
+            s = windows * seq_len
+            self.inner.score(streams[:, s:s + rest], streams[:, s + 1:s + 1 + rest], state=state, accum=accum)
+        return accum
+
+    def evaluate(self, corpus: CharCorpus, batch: int, seq_len: Optional[int] = None) -> Dict[str, float]:
+        """Held-out loss of ``corpus``: cut into ``batch`` parallel streams,
+        consecutive ``seq_len`` windows (default: the training length) scored
+        with the state carried from window to window, the first from zeros, so
+        every stream is scored as one sequence whatever ``seq_len`` is.
+        Returns loss (nats per token), bpc, accuracy, tokens, duration and
+        tokens_per_sec; the sums stay on the device until one read at the end.
+
+        The model's mode, its TBPTT carry and its parameters are untouched.  A
+        persistent-recurrence launch that lost co-residency (per-step
+        verification) never reaches the figures: the evaluation is run again on
+        the per-step kernels and the sticky flag is cleared."""
+        seq_len = int(seq_len or self.seq_len)
+        if batch < 1 or seq_len < 1:
+            raise ValueError("evaluate: batch and seq_len must be at least 1")
+        streams = corpus.streams(batch).to(self.device)
+        if streams.shape[1] < 2:
+            raise ValueError(f"evaluate: {len(corpus)} tokens are too few for {batch} streams")
+        self.settle()  # no unverified training step (and its sticky flag) behind this evaluation
+        t0 = time.perf_counter()
+        total = self._score_streams(streams, seq_len).cpu()  # the evaluation's one read
+        if self._deferred_verify() and _ext.extension().persist_step_check():
+            # a launch of this evaluation timed out: the flag is cleared and the persistent path off
+            _ext.extension().persist_disable()
+            total = self._score_streams(streams, seq_len).cpu()
+        dt = time.perf_counter() - t0
+        nll, n, correct = (float(v) for v in total)
+        loss = nll / n if n else float("nan")
+        return {"loss": loss, "bpc": loss / math.log(2), "accuracy": correct / n if n else float("nan"),
+                "tokens": int(n), "duration": dt, "tokens_per_sec": n / dt if dt else 0.0}
 
     # ------------------------------------------------------------ checkpoints
     def save(self, path, epoch: int, loss: float):
