@@ -657,11 +657,26 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
   check_stack(w, NL, H, I, has_bias);
   TORCH_CHECK(has_bias, "fused train step expects LSTM biases");
   const bool gathered = idx.has_value() && idx->defined();
+  if (gathered)
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1 && idx->is_contiguous() &&
+                idx->device() == x.device(), "idx must be a contiguous 1-D int64 tensor on x's device");
   const int64_t B = gathered ? idx->size(0) : x.size(0);
   const int64_t T = x.size(1);
+  TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H && head_w.is_contiguous() &&
+              head_w.scalar_type() == at::kFloat && head_w.device() == x.device(),
+              "head weight must be fp32 [C, H] on x's device");
   const int64_t C = head_w.size(0);
-  TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H && head_w.is_contiguous() && C <= 16, "head weight [C<=16, H]");
-  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous(), "labels must be int64");
+  TORCH_CHECK(C >= 1 && C <= 16, "fused train step serves 1..16 classes, got ", C);
+  const bool has_hb = head_b.has_value() && head_b->defined();
+  if (has_hb)
+    TORCH_CHECK(head_b->numel() == C && head_b->is_contiguous() && head_b->scalar_type() == at::kFloat &&
+                head_b->device() == x.device(), "head bias must be fp32 [C] on x's device");
+  // the label of row b is labels[idx[b]] (gathered: one per row of the table) or labels[b]
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.device() == x.device() &&
+              (gathered ? labels.numel() >= x.size(0) : labels.numel() == B),
+              "labels must be int64 on x's device, one per row of x");
+  TORCH_CHECK(flat_grad.device() == x.device() && stats.device() == x.device(),
+              "flat_grad and stats must be on x's device");
   StackLayout L = stack_layout(w, NL, true);
   // GRU: `w` is the packed 4-block stack; the flat gradient buffer holds
   // nn.GRU's parameters, reached from the packed slab through grad_colmap
@@ -757,32 +772,8 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
     dw.B = (int)B; dw.T = (int)T; dw.I = (int)I; dw.NL = (int)NL; dw.chunks = p.slab_rows;
   }
 
-  // ---- launch
-  hipStream_t st = cur_stream();
-  if (p.sw_step) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_step(&f, &bk, st));
-  else if (p.one_launch) HIP_LAUNCH_CHECK(pdrnn_lstm_small_step(&f, &bk, (int)H, st));
-  else {
-    HIP_LAUNCH_CHECK(sw ? pdrnn_lstm_sw_fwd(&f, p.sw_fmode, st)
-                        : pdrnn_lstm_small_fwd(&f, (int)H, p.nb_fwd, p.split_fwd, 1, st));
-    HIP_LAUNCH_CHECK(sw      ? pdrnn_lstm_sw_bwd(&bk, p.sw_bmode, st)
-                     : dwout ? pdrnn_lstm_small_bwd_dwout(&bk, (int)H, p.grid_dw, p.nb_dw, st)
-                             : pdrnn_lstm_small_bwd(&bk, (int)H, p.nb_bwd, p.split_bwd, p.gridb, st));
-  }
-  if (dwout && !p.sw_rdw) HIP_LAUNCH_CHECK(pdrnn_lstm_small_dw(&dw, (int)H, st));
-  if (st_f.defined()) {
-    const int bw_iters = sw ? (int)(T + NL - 1)
-                            : (int)(T + 2 * (NL - 1)) *
-                                  (int)((B + (int64_t)p.grid_dw * p.nb_dw - 1) / ((int64_t)p.grid_dw * p.nb_dw));
-    if (p.phase) report_phase_stamps(st_f);
-    report_stamps(sw ? "fwd(head step, seq-in-wave)" : "fwd(head step)",
-                  p.phase ? st_f.narrow(1, 0, 8).contiguous() : st_f, (int)(T + NL - 1));
-    report_stamps(sw ? "bwd(head step, seq-in-wave, deferred dW)"
-                     : dwout ? "bwd(head step, lean, deferred dW)" : "bwd(head step, lean)",
-                  st_b, bw_iters);
-  }
-
-  // one-pass reduction of the slabs into the flat gradient (+ batch statistics),
-  // with Adam folded in for a single process (slab_reduce_adam_kernel)
+  // ---- Adam folded into the reduction for a single process (slab_reduce_adam_kernel):
+  // its operands, checked like every other argument ahead of the first launch
   PdrnnAdamArgs ad{};
   const bool fold_adam = adam_state.has_value() && adam_hp.has_value();
   if (fold_adam) {
@@ -808,6 +799,32 @@ void lstm_head_train_step(const Tensor& x, const optional<Tensor>& idx, const Te
       ad.ticket = reinterpret_cast<unsigned int*>(adam_ticket->data_ptr<int>());
     }
   }
+
+  // ---- launch
+  hipStream_t st = cur_stream();
+  if (p.sw_step) HIP_LAUNCH_CHECK(pdrnn_lstm_sw_step(&f, &bk, st));
+  else if (p.one_launch) HIP_LAUNCH_CHECK(pdrnn_lstm_small_step(&f, &bk, (int)H, st));
+  else {
+    HIP_LAUNCH_CHECK(sw ? pdrnn_lstm_sw_fwd(&f, p.sw_fmode, st)
+                        : pdrnn_lstm_small_fwd(&f, (int)H, p.nb_fwd, p.split_fwd, 1, st));
+    HIP_LAUNCH_CHECK(sw      ? pdrnn_lstm_sw_bwd(&bk, p.sw_bmode, st)
+                     : dwout ? pdrnn_lstm_small_bwd_dwout(&bk, (int)H, p.grid_dw, p.nb_dw, st)
+                             : pdrnn_lstm_small_bwd(&bk, (int)H, p.nb_bwd, p.split_bwd, p.gridb, st));
+  }
+  if (dwout && !p.sw_rdw) HIP_LAUNCH_CHECK(pdrnn_lstm_small_dw(&dw, (int)H, st));
+  if (st_f.defined()) {
+    const int bw_iters = sw ? (int)(T + NL - 1)
+                            : (int)(T + 2 * (NL - 1)) *
+                                  (int)((B + (int64_t)p.grid_dw * p.nb_dw - 1) / ((int64_t)p.grid_dw * p.nb_dw));
+    if (p.phase) report_phase_stamps(st_f);
+    report_stamps(sw ? "fwd(head step, seq-in-wave)" : "fwd(head step)",
+                  p.phase ? st_f.narrow(1, 0, 8).contiguous() : st_f, (int)(T + NL - 1));
+    report_stamps(sw ? "bwd(head step, seq-in-wave, deferred dW)"
+                     : dwout ? "bwd(head step, lean, deferred dW)" : "bwd(head step, lean)",
+                  st_b, bw_iters);
+  }
+
+  // one-pass reduction of the slabs into the flat gradient (+ batch statistics)
   HIP_LAUNCH_CHECK(pdrnn_slab_reduce_adam(fold_adam ? &ad : nullptr, slab.data_ptr<float>(), p.slab_rows, P_rnn, L.P,
                                           colmap, head_slab.data_ptr<float>(), B, PH, P_params,
                                           flat_grad.data_ptr<float>(), stats.data_ptr<float>(), slot_step,
