@@ -17,7 +17,12 @@ reference call of ``--tokens`` tokens (for a ``rocprofv3 --kernel-trace
 --stats`` run of its own; the per-token kernel table is its totals over the
 token count).
 
+``--top-k K`` / ``--top-p P`` / ``--logprobs``: both paths sample through the
+filters (and return the tokens' log-probabilities); the defaults are off, which
+is the plain sampler the figures of profiles/r11 were taken with.
+
     python bench/decode_bench.py [--pairs 5] [--warmup 2] [--tokens 512] [--batches 1 4 16] [--out FILE]
+                                 [--top-k 40] [--top-p 0.9] [--logprobs]
 """
 from __future__ import annotations
 
@@ -47,6 +52,9 @@ def main(argv=None) -> int:
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0, help="0: off")
+    ap.add_argument("--top-p", type=float, default=1.0, help="1: off")
+    ap.add_argument("--logprobs", action="store_true", help="also return the tokens' log-probabilities")
     ap.add_argument("--profile-one", type=int, default=None, metavar="B")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args(argv)
@@ -68,7 +76,9 @@ def main(argv=None) -> int:
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
-                tokens = model.generate(prompt, args.tokens, temperature=args.temperature, seed=1)
+                out = model.generate(prompt, args.tokens, temperature=args.temperature, seed=1, top_k=args.top_k,
+                                     top_p=args.top_p, return_logprobs=args.logprobs)
+            tokens = out[0] if args.logprobs else out
             return tokens.cpu()  # (the host read a caller ends with)
         finally:
             dec.supported = real_supported
@@ -85,7 +95,8 @@ def main(argv=None) -> int:
         assert real_supported(args.profile_one, args.hidden, args.embed, args.vocab, args.layers, cdt, dev)
         for _ in range(args.warmup):
             generate(prompt, False), generate(prompt, True)
-        print(json.dumps({"profile_one": args.profile_one, "tokens": args.tokens,
+        print(json.dumps({"profile_one": args.profile_one, "tokens": args.tokens, "top_k": args.top_k,
+                          "top_p": args.top_p, "logprobs": args.logprobs,
                           "reference_us_per_token": round(timed(prompt, False), 2),
                           "fused_us_per_token": round(timed(prompt, True), 2)}), flush=True)
         return 0
@@ -100,6 +111,7 @@ def main(argv=None) -> int:
         pairs = [(timed(prompt, False), timed(prompt, True)) for _ in range(args.pairs)]
         old, fused = [p[0] for p in pairs], [p[1] for p in pairs]
         rec = {"B": B, "tokens": args.tokens, "model": f"{args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
+               "top_k": args.top_k, "top_p": args.top_p, "logprobs": args.logprobs,
                "pairs_us_per_token": [[round(a, 2), round(b, 2)] for a, b in pairs],
                "reference_us_per_token": {"median": round(statistics.median(old), 2), "min": round(min(old), 2),
                                           "max": round(max(old), 2)},

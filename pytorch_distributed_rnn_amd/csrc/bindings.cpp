@@ -1806,7 +1806,8 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
                  const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
                  const Tensor& c, const Tensor& scratch, const Tensor& first, const optional<Tensor>& forced,
                  const Tensor& tokens, const optional<Tensor>& logits, double temperature, int64_t seed,
-                 int64_t stream0, int64_t pos0) {
+                 int64_t stream0, int64_t pos0, int64_t top_k, double top_p, const optional<Tensor>& threshold,
+                 const optional<Tensor>& logprobs) {
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
   const int dt = dtype_code(emb);
@@ -1845,6 +1846,11 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
                                    "lstm_decode: forced [B, N] int64");
   if (present(logits)) TORCH_CHECK(f32(*logits) && logits->numel() == B * N * V, "lstm_decode: logits [B, N, V] fp32");
   TORCH_CHECK(temperature >= 0.0, "lstm_decode: temperature >= 0");
+  TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, "lstm_decode: top_k >= 0 (0: off)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "lstm_decode: top_p in (0, 1] (1: off)");
+  for (const optional<Tensor>* o : {&threshold, &logprobs})
+    if (present(*o)) TORCH_CHECK(f32(**o) && (*o)->dim() == 2 && (*o)->size(0) == B && (*o)->size(1) == N,
+                                 "lstm_decode: threshold / logprobs [B, N] fp32, contiguous, on the device");
   PdrnnLstmDecodeArgs a{};
   a.emb = emb.data_ptr();
   a.w_ih = pi.data();
@@ -1865,6 +1871,10 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
   a.seed = (uint32_t)seed;
   a.stream0 = (uint32_t)stream0;
   a.pos0 = (uint32_t)pos0;
+  a.top_k = (int)top_k;
+  a.top_p = (float)top_p;
+  a.threshold = present(threshold) ? threshold->data_ptr<float>() : nullptr;
+  a.logprobs = present(logprobs) ? logprobs->data_ptr<float>() : nullptr;
   HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
 }
 
@@ -2072,7 +2082,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_decode", &lstm_decode, "char-LM generation: n_tokens positions of the fused decode kernels",
         py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
         py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("forced"), py::arg("tokens"),
-        py::arg("logits"), py::arg("temperature"), py::arg("seed"), py::arg("stream0"), py::arg("pos0"));
+        py::arg("logits"), py::arg("temperature"), py::arg("seed"), py::arg("stream0"), py::arg("pos0"),
+        py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("threshold") = py::none(),
+        py::arg("logprobs") = py::none());
   m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
     return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
   }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");

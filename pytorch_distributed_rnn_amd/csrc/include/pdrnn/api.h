@@ -505,11 +505,17 @@ typedef struct {
   int dtype;                 // 0 bf16, 1 fp16
   float temperature;
   uint32_t seed, stream0, pos0;
+  // the sampling filters and their outputs (pdrnn/decode_rng.h: the rule); all zero: off / not wanted
+  int top_k;                 // keep the logits >= the k-th largest; 0 or >= V: off
+  float top_p;               // then the smallest head of them holding top_p of their mass; 0 or >= 1: off
+  float* threshold;          // [B, n_tokens] or NULL: the smallest kept logit, -inf with both filters off
+  float* logprobs;           // [B, n_tokens] or NULL: log-probability of tokens[b, p] under the kept distribution
 } PdrnnLstmDecodeArgs;
 // B <= 16, H % 64 == 0, E % 32 == 0, V <= 1024, 16-bit storage
 int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype);
 // Enqueues (L + 1) * n_tokens launches and a last sampling-only one; no host
-// read.  Every 16-bit pointer 16-byte aligned.
+// read.  Every 16-bit pointer 16-byte aligned.  top_k < 0 and a negative or
+// NaN top_p are hipErrorInvalidValue.
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
 
 // ---- char-LM evaluation (kernels/head_nll.hip) ------------------------------

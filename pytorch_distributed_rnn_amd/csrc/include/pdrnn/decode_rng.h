@@ -48,4 +48,37 @@ PDRNN_RNG_FN float decode_uniform(uint32_t r) {
   return u < 0.99999994f ? u : 0.99999994f;
 }
 
+// ---- top-k and nucleus filtering --------------------------------------------
+// Gumbel-max needs no sorted distribution: a filter is a per-row threshold tau,
+// token = argmax over {v : l_v >= tau} of l_v / T + g_v, with g_v the noise
+// above, drawn for the same v whatever the filter (ops/decode.py:keep_threshold
+// mirrors the rule).  For fp32 logits l_v, temperature T > 0, top_k, top_p:
+//   1. top-k on the raw logits: tau_k = the k-th largest l_v counted with
+//      multiplicity (top_k = 0 or >= V: off, tau_k = -inf).  l_v >= tau_k is
+//      kept: everything tied with the k-th survives, no index tie-break.
+//   2. top-p over those survivors, renormalised: y_v = l_v / T, w_v =
+//      exp(y_v - max y); tau_p = the largest logit value tau with
+//      sum{w_v : l_v >= tau} >= top_p * sum{w_v : l_v >= tau_k}  (top_p = 0 or
+//      >= 1: off).  Ties at the boundary are all kept.
+//   3. tau = max(tau_k, tau_p), the smallest kept logit (-inf: both off).
+//   4. log-prob of the drawn token: y_tok - max y - log(sum{w_v : l_v >= tau}).
+//   5. Temperature 0 (greedy) ignores both filters; its log-prob is the
+//      argmax's under T = 1, unfiltered.
+// -inf logits are ordinary values of weight 0.  -0 counts as +0.
+//
+// The threshold is found by selection over order-preserving 32-bit keys of the
+// logits: larger float <=> larger unsigned key.
+PDRNN_RNG_FN uint32_t decode_order_key(float x) {
+  uint32_t u;
+  __builtin_memcpy(&u, &x, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+PDRNN_RNG_FN float decode_key_value(uint32_t k) {
+  const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+  float x;
+  __builtin_memcpy(&x, &u, 4);
+  return x;
+}
+
 }  // namespace pdrnn

@@ -17,7 +17,9 @@
 //     prompt's last, or sampled from the previous position's logits -- and
 //     reads x_t straight from that row of the 16-bit embedding.  Every
 //     workgroup samples the same B tokens on its own (B x V values, an argmax);
-//     workgroup 0 alone records them.
+//     workgroup 0 alone records them.  With a top-k / nucleus filter or the
+//     log-probs wanted, the FILT instantiation first finds each row's keep
+//     threshold by a bitwise selection in registers (sample_tokens_filtered).
 //   * lstm_decode_head<DT>: logits = h_top W_fc^T + b_fc in fp32, 16
 //     vocabulary rows per workgroup, rows past V masked.
 // h ping-pongs between two buffers by token parity (every workgroup reads all
@@ -67,6 +69,11 @@ struct SampleArgs {
   int B, V, N;
   float temperature;      // 0: greedy
   uint32_t seed, stream0, pos0;
+  // the filtered sampler only (sample_tokens_filtered)
+  int top_k;              // 0: off
+  float top_p;            // 0 or >= 1: off
+  float* threshold;       // [B, N] or null
+  float* logprobs;        // [B, N] or null
 };
 
 // tok[b] = argmax_v(logit / T + g), the lowest index on ties, for every stream
@@ -97,6 +104,167 @@ __device__ __forceinline__ void sample_tokens(const SampleArgs& s, int p, int* t
   }
 }
 
+constexpr int kSlots = 16;  // logits a lane holds at the most: ceil(1024 / 64)
+
+// x (op) the value of another lane of the row of 16, by a DPP control
+template <int CTRL>
+__device__ __forceinline__ float dpp_peer(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float lane_value(float x, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
+}
+
+// Wave-wide sum in a fixed order, no LDS path.  Within a row of 16 lanes a
+// butterfly: the lanes paired at a stage add the same two values (a + b and
+// b + a: the same bits), so the row's lanes end equal -- quad_perm [1 0 3 2],
+// [2 3 0 1], then row_half_mirror and row_mirror, which pair a lane with one of
+// the other, already equal, quad or half.  The four row sums are then read out
+// and added as (r0 + r1) + (r2 + r3) in every lane.  Every wave of every
+// workgroup that starts from the same row ends with the same bits.
+__device__ __forceinline__ float wave_sum(float x) {
+  x += dpp_peer<0xb1>(x);
+  x += dpp_peer<0x4e>(x);
+  x += dpp_peer<0x141>(x);
+  x += dpp_peer<0x140>(x);
+  return (lane_value(x, 0) + lane_value(x, 16)) + (lane_value(x, 32) + lane_value(x, 48));
+}
+
+__device__ __forceinline__ float wave_max(float x) {
+  x = fmaxf(x, dpp_peer<0xb1>(x));
+  x = fmaxf(x, dpp_peer<0x4e>(x));
+  x = fmaxf(x, dpp_peer<0x141>(x));
+  x = fmaxf(x, dpp_peer<0x140>(x));
+  return fmaxf(fmaxf(lane_value(x, 0), lane_value(x, 16)), fmaxf(lane_value(x, 32), lane_value(x, 48)));
+}
+
+// sum{w : key >= t}: a lane's slots in order, then wave_sum.  The terms are
+// >= 0 and rounding is monotone, so the sum does not grow with t.
+template <int NS>
+__device__ __forceinline__ float mass_at_least(const uint32_t (&key)[NS], const float (&w)[NS], uint32_t t) {
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) acc += key[i] >= t ? w[i] : 0.f;
+  return wave_sum(acc);
+}
+
+// |{key >= t}|, t > 0 (slots past V hold key 0)
+template <int NS>
+__device__ __forceinline__ int count_at_least(const uint32_t (&key)[NS], uint32_t t) {
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(key[i] >= t));
+  return n;
+}
+
+// sample_tokens with the filters of pdrnn/decode_rng.h: the same draw over the
+// entries l_v >= tau, and thr[b] = tau, lp[b] = the drawn token's log-prob
+// under the kept distribution.  A lane holds entries lane, lane + 64, ... of
+// the row (NS >= V / 64 of them) in registers, as values, as order-preserving
+// keys and (where a mass is needed) as weights w = exp(y - max y).  tau's key
+// is built bit by bit from the top: a bit stays set while the entries at or
+// above the candidate still number top_k (wave ballots) or still weigh top_p
+// of the top-k survivors (mass_at_least) -- the largest key with that property
+// is an entry's own.  Counts are integers and the sums are the same
+// instructions on the same values in every workgroup: all of them find the
+// same tau and token.
+template <int NS>
+__device__ __forceinline__ void sample_tokens_filtered_n(const SampleArgs& s, int p, int* tok, float* thr, float* lp) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int V = s.V;
+  const bool greedy = s.temperature == 0.f;  // no filter, log-prob at T = 1
+  const float T = greedy ? 1.f : s.temperature;
+  const int top_k = (!greedy && s.top_k > 0 && s.top_k < V) ? s.top_k : 0;
+  const bool nucleus = !greedy && s.top_p > 0.f && s.top_p < 1.f;
+  const bool mass = nucleus || s.logprobs != nullptr;
+  for (int b = wave; b < s.B; b += kWaves) {
+    const uint32_t hkey = decode_key(s.seed, s.stream0 + (uint32_t)b, s.pos0 + (uint32_t)p);
+    const float* row = s.scratch + (int64_t)b * V;
+    float l[NS], w[NS];
+    uint32_t key[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {  // every load in flight at once: the index held inside the row
+      const int v = lane + i * kWave;
+      l[i] = row[v < V ? v : V - 1];
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const bool in = lane + i * kWave < V;
+      l[i] = !in ? -INFINITY : l[i] == 0.f ? 0.f : l[i];  // (-0 counts as +0)
+      key[i] = in ? decode_order_key(l[i]) : 0;
+      m = fmaxf(m, l[i] / T);
+      w[i] = 0.f;
+    }
+    if (mass) {
+      m = wave_max(m);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) w[i] = expf(l[i] / T - m);  // (slots past V: exp(-inf) = 0)
+    }
+
+    uint32_t t = 0;
+    if (top_k) {
+#pragma unroll 1
+      for (uint32_t bit = 0x80000000u; bit != 0; bit >>= 1)
+        if (count_at_least<NS>(key, t | bit) >= top_k) t |= bit;
+    }
+    if (nucleus) {
+      // over the top-k survivors: their mass is the target's base, and the
+      // search ends at or above t since mass(t) >= top_p mass(t)
+      const float target = s.top_p * mass_at_least<NS>(key, w, t);
+      uint32_t tp = 0;
+#pragma unroll 1
+      for (uint32_t bit = 0x80000000u; bit != 0; bit >>= 1)
+        if (mass_at_least<NS>(key, w, tp | bit) >= target) tp |= bit;
+      t = tp > t ? tp : t;
+    }
+    const float tau = (top_k || nucleus) ? decode_key_value(t) : -INFINITY;
+
+    float best = -INFINITY;
+    int bi = V;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int v = lane + i * kWave;
+      if (v < V && l[i] >= tau) {
+        float val = l[i];
+        if (!greedy) {
+          const float u = decode_uniform(decode_word(hkey, (uint32_t)v));
+          val = val / s.temperature + -logf(-logf(u));
+        }
+        if (val > best) { best = val; bi = v; }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    bi = bi < V ? bi : 0;  // (all-NaN logits: a valid row all the same)
+    float lpv = 0.f;
+    if (s.logprobs != nullptr) {
+      float acc = 0.f;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) acc += l[i] >= tau ? w[i] : 0.f;
+      lpv = row[bi] / T - m - logf(wave_sum(acc));
+    }
+    if (lane == 0) {
+      tok[b] = bi;
+      thr[b] = tau;
+      lp[b] = lpv;
+    }
+  }
+}
+
+// (the slot count is the launch's: V is uniform)
+__device__ __forceinline__ void sample_tokens_filtered(const SampleArgs& s, int p, int* tok, float* thr, float* lp) {
+  if (s.V <= 1 * kWave) sample_tokens_filtered_n<1>(s, p, tok, thr, lp);
+  else if (s.V <= 2 * kWave) sample_tokens_filtered_n<2>(s, p, tok, thr, lp);
+  else if (s.V <= 4 * kWave) sample_tokens_filtered_n<4>(s, p, tok, thr, lp);
+  else if (s.V <= 8 * kWave) sample_tokens_filtered_n<8>(s, p, tok, thr, lp);
+  else sample_tokens_filtered_n<kSlots>(s, p, tok, thr, lp);
+}
+
 struct LayerArgs {
   const uint16_t* wx;     // [4H, Kx] gate-interleaved rows 4u + q
   const uint16_t* wh;     // [4H, H]
@@ -122,10 +290,13 @@ __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
   return sum;
 }
 
-template <class DT, bool FIRST>
+// FILT (layer 0 only, chosen on the host): the filtered sampler and its two
+// outputs; a launch sequence with no filter and no output wanted never runs it.
+template <class DT, bool FIRST, bool FILT = false>
 __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a) {
   __shared__ f32x4 red[kWaves][kWave];
   __shared__ int tok[kStreams];
+  __shared__ float thr[FILT ? kStreams : 1], lp[FILT ? kStreams : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, kq = lane >> 4;
   const int B = a.s.B, H = a.H, Kx = a.Kx;
@@ -136,10 +307,19 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
     // the sampled token is needed as an input only when nothing is forced;
     // forced runs still record it, which is workgroup 0's job alone
     const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
-    if (sample) sample_tokens(a.s, a.p - 1, tok);
+    if (sample) {
+      if constexpr (FILT) sample_tokens_filtered(a.s, a.p - 1, tok, thr, lp);
+      else sample_tokens(a.s, a.p - 1, tok);
+    }
     __syncthreads();
-    if (sample && blockIdx.x == 0 && threadIdx.x < B)
-      a.s.tokens[(int64_t)threadIdx.x * a.s.N + a.p - 1] = tok[threadIdx.x];
+    if (sample && blockIdx.x == 0 && threadIdx.x < B) {
+      const int64_t at = (int64_t)threadIdx.x * a.s.N + a.p - 1;
+      a.s.tokens[at] = tok[threadIdx.x];
+      if constexpr (FILT) {
+        if (a.s.threshold != nullptr) a.s.threshold[at] = thr[threadIdx.x];
+        if (a.s.logprobs != nullptr) a.s.logprobs[at] = lp[threadIdx.x];
+      }
+    }
     int64_t t = 0;
     if (live) {
       if (a.forced != nullptr) t = a.forced[(int64_t)n * a.s.N + a.p];
@@ -227,17 +407,31 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_head(const HeadArgs a) {
 }
 
 // The last token: sampled from the last position's logits, recorded, fed to nothing.
+template <bool FILT>
 __global__ __launch_bounds__(kThreads) void lstm_decode_sample(const SampleArgs s) {
   __shared__ int tok[kStreams];
-  sample_tokens(s, s.N - 1, tok);
+  __shared__ float thr[FILT ? kStreams : 1], lp[FILT ? kStreams : 1];
+  if constexpr (FILT) sample_tokens_filtered(s, s.N - 1, tok, thr, lp);
+  else sample_tokens(s, s.N - 1, tok);
   __syncthreads();
-  if (threadIdx.x < s.B) s.tokens[(int64_t)threadIdx.x * s.N + s.N - 1] = tok[threadIdx.x];
+  if (threadIdx.x < s.B) {
+    const int64_t at = (int64_t)threadIdx.x * s.N + s.N - 1;
+    s.tokens[at] = tok[threadIdx.x];
+    if constexpr (FILT) {
+      if (s.threshold != nullptr) s.threshold[at] = thr[threadIdx.x];
+      if (s.logprobs != nullptr) s.logprobs[at] = lp[threadIdx.x];
+    }
+  }
 }
 
 template <class DT>
 hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
   const int B = a->B, H = a->H, E = a->E, V = a->V, L = a->L;
-  const SampleArgs s{a->scratch, a->tokens, B, V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0};
+  const bool top_k = a->top_k > 0 && a->top_k < V, top_p = a->top_p > 0.f && a->top_p < 1.f;
+  // the filtered sampler only where it has something to do: a filter at T > 0, or an output to fill
+  const bool filt = (a->temperature != 0.f && (top_k || top_p)) || a->threshold != nullptr || a->logprobs != nullptr;
+  const SampleArgs s{a->scratch, a->tokens, B, V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0,
+                     top_k ? a->top_k : 0, top_p ? a->top_p : 0.f, a->threshold, a->logprobs};
   const uint16_t* h = static_cast<const uint16_t*>(a->h);
   uint16_t* hm = static_cast<uint16_t*>(a->h);
   const int64_t BH = (int64_t)B * H, slot = (int64_t)L * BH;
@@ -258,7 +452,8 @@ hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream
       k.H = H;
       k.Kx = l == 0 ? E : H;
       k.p = p;
-      if (l == 0) lstm_decode_layer<DT, true><<<H / 4, kThreads, 0, stream>>>(k);
+      if (l == 0 && filt) lstm_decode_layer<DT, true, true><<<H / 4, kThreads, 0, stream>>>(k);
+      else if (l == 0) lstm_decode_layer<DT, true><<<H / 4, kThreads, 0, stream>>>(k);
       else lstm_decode_layer<DT, false><<<H / 4, kThreads, 0, stream>>>(k);
       PDRNN_HIP_CHECK(hipGetLastError());
     }
@@ -267,7 +462,8 @@ hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream
     lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
     PDRNN_HIP_CHECK(hipGetLastError());
   }
-  lstm_decode_sample<<<1, kThreads, 0, stream>>>(s);
+  if (filt) lstm_decode_sample<true><<<1, kThreads, 0, stream>>>(s);
+  else lstm_decode_sample<false><<<1, kThreads, 0, stream>>>(s);
   return hipGetLastError();
 }
 
@@ -283,7 +479,7 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype) {
 
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
   if (n_tokens < 1 || !pdrnn_lstm_decode_supported(a->B, a->H, a->E, a->V, a->L, a->dtype)) return hipErrorInvalidValue;
-  if (!(a->temperature >= 0.f)) return hipErrorInvalidValue;
+  if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
   return a->dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
 }
 

@@ -6,7 +6,8 @@
         -m pytorch_distributed_rnn_amd.lm_cli ... distributed
 
     python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-epoch0.pt \\
-        --prompt "The " --num-tokens 256 --temperature 0.8 --samples 4 generate
+        --prompt "The " --num-tokens 256 --temperature 0.8 --top-k 40 --top-p 0.9 --stop-token 10 \\
+        --samples 4 generate
 
     python -m pytorch_distributed_rnn_amd.lm_cli --text corpus.txt --validation-fraction 0.1 \\
         --checkpoint-directory out local
@@ -77,6 +78,13 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--prompt-file", default=None, help="the prompt's bytes from a file instead")
     g.add_argument("--num-tokens", type=int, default=256)
     g.add_argument("--temperature", type=float, default=1.0, help="0: greedy")
+    g.add_argument("--top-k", type=int, default=0, help="generate: sample among the k most likely bytes (ties with "
+                                                       "the k-th kept); 0: off")
+    g.add_argument("--top-p", type=float, default=1.0, help="generate: then among the most likely of them that hold "
+                                                         "this share of their probability; 1: off")
+    g.add_argument("--stop-token", type=int, default=None, help="generate: a byte value; a sample ends before its first one")
+    g.add_argument("--logprobs-file", default=None, help="generate: write every sample's token log-probabilities "
+                                                         "(under the filtered distribution) and their sum here as JSON")
     g.add_argument("--samples", type=int, default=1)
     g.add_argument("--output", default=None, help="generate: write the samples' raw bytes here, one after another; "
                                                    "evaluate: write the figures here as JSON")
@@ -113,6 +121,8 @@ def generate(args):
         raise SystemExit("generate: give --prompt or --prompt-file, not both")
     if args.samples < 1 or args.num_tokens < 0 or args.temperature < 0:
         raise SystemExit("generate: --samples >= 1, --num-tokens >= 0 and --temperature >= 0")
+    if args.top_k < 0 or not 0 < args.top_p <= 1:
+        raise SystemExit("generate: --top-k >= 0 and --top-p in (0, 1]")
     if args.prompt_file is not None:
         with open(args.prompt_file, "rb") as f:
             prompt = f.read()
@@ -125,11 +135,22 @@ def generate(args):
         raise SystemExit(f"generate: a vocabulary of {model.vocab_size} entries is not bytes")
     if max(prompt) >= model.vocab_size:
         raise SystemExit(f"generate: the prompt holds byte {max(prompt)}, the model's vocabulary is {model.vocab_size}")
+    if args.stop_token is not None and not 0 <= args.stop_token < model.vocab_size:
+        raise SystemExit(f"generate: --stop-token {args.stop_token} is outside the model's vocabulary of {model.vocab_size}")
     device = torch.device(args.device) if args.device else default_device()
     model = model.to(device).eval()
-    tokens = model.generate(torch.tensor(list(prompt), dtype=torch.int64).repeat(args.samples, 1), args.num_tokens,
-                            temperature=args.temperature, seed=args.seed)
-    samples = [bytes(row) for row in tokens.cpu().tolist()]  # (a 256-entry vocabulary at the most: bytes)
+    want_lp = args.logprobs_file is not None
+    out = model.generate(torch.tensor(list(prompt), dtype=torch.int64).repeat(args.samples, 1), args.num_tokens,
+                         temperature=args.temperature, seed=args.seed, top_k=args.top_k, top_p=args.top_p,
+                         stop=args.stop_token, return_logprobs=want_lp, return_lengths=True)
+    tokens, lengths = out[0].cpu().tolist(), out[-1].cpu().tolist()
+    logprobs = out[1].double().cpu() if want_lp else None
+    # a sample ends before its stop byte; its log-probs include the stop's
+    samples = [bytes(row[:n - 1] if n and row[n - 1] == args.stop_token else row[:n]) for row, n in zip(tokens, lengths)]
+    if want_lp:
+        with open(args.logprobs_file, "w") as f:
+            json.dump({"samples": [{"length": n, "logprobs": lp[:n].tolist(), "sum": float(lp[:n].sum())}
+                                   for lp, n in zip(logprobs, lengths)]}, f)
     if args.output:
         with open(args.output, "wb") as f:
             f.write(b"".join(samples))

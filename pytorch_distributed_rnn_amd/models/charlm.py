@@ -70,9 +70,11 @@ class CharLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompt: Tensor, num_tokens: int, temperature: float = 1.0, seed: int = 0,
                  state: Optional[Tuple[Tensor, Tensor]] = None, forced: Optional[Tensor] = None,
-                 return_logits: bool = False, return_state: bool = False):
+                 return_logits: bool = False, return_state: bool = False, top_k: int = 0, top_p: float = 1.0,
+                 stop: Optional[int] = None, return_logprobs: bool = False, return_lengths: bool = False):
         """Sample ``num_tokens`` tokens after ``prompt`` [B, P] (P >= 1) ->
         tokens [B, num_tokens] int64 (, logits [B, num_tokens, V] fp32)
+        (, log-probs [B, num_tokens] fp32) (, lengths [B] int64)
         (, (h, c) [layers, B, H], c in fp32 on the fused path).
 
         The rule is ops/decode.py's: ``token = argmax(logits / temperature +
@@ -82,6 +84,17 @@ class CharLM(nn.Module):
         (zeros when None); the last prompt token is the first input.
         ``forced`` [B, num_tokens] replaces every position's input token (the
         sampled ones are still returned): scoring a given continuation.
+
+        ``top_k`` / ``top_p`` restrict the draw to the k largest logits (ties
+        with the k-th kept) and then to the smallest head of them that holds
+        ``top_p`` of their probability; the log-probs are the drawn tokens'
+        under that kept, renormalised distribution (ops/decode.py: the rule).
+        ``stop``: from a row's first sampled ``stop`` token on, its tokens are
+        ``stop`` and its log-probs 0; ``lengths`` counts a row's tokens up to
+        and including that first ``stop`` (``num_tokens`` without one).  The
+        rows are independent and all launches are enqueued up front, so
+        ``stop`` is applied to the finished batch, on the device, with no host
+        read; the logits and the state are those of the full run.
 
         On the GPU, 16-bit models the decode kernels cover run on them
         (kernels/lstm_decode.hip; more than 16 rows as independent groups of
@@ -99,6 +112,11 @@ class CharLM(nn.Module):
         N = int(num_tokens)
         if forced is not None and tuple(forced.shape) != (B, N):
             raise ValueError("generate: forced must be [B, num_tokens]")
+        dec.check_filters(top_k, top_p)
+        if stop is not None and forced is not None:
+            raise ValueError("generate: stop and forced exclude each other")
+        if stop is not None and not 0 <= int(stop) < self.vocab_size:
+            raise ValueError(f"generate: stop token {stop} is outside the vocabulary")
         for name, t in (("prompt", prompt), ("forced", forced)):
             if t is not None and t.device.type == "cpu" and t.numel() and not (0 <= int(t.min()) and int(t.max()) < self.vocab_size):
                 raise ValueError(f"generate: {name} holds tokens outside the vocabulary")
@@ -111,6 +129,8 @@ class CharLM(nn.Module):
             first = prompt[:, -1]
             cdt = self._cdt(dev)
             plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+            logprobs = None
+            filt = dict(top_k=top_k, top_p=top_p, return_logprobs=return_logprobs)
             if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev):
                 outs = []
                 for b0 in range(0, B, dec.MAX_STREAMS):
@@ -119,25 +139,39 @@ class CharLM(nn.Module):
                         self.embedding.weight, self.lstm._weights(), self.fc.weight, self.fc.bias, cdt,
                         state[0][:, rows] if state is not None else None, state[1][:, rows] if state is not None else None,
                         first[rows], N, temperature=temperature, seed=seed, stream0=b0, pos0=P,
-                        forced=forced[rows] if forced is not None else None, return_logits=return_logits))
+                        forced=forced[rows] if forced is not None else None, return_logits=return_logits, **filt))
                 if len(outs) == 1:
-                    tokens, logits, h, c = outs[0]
+                    tokens, logits, h, c = outs[0][:4]
+                    logprobs = outs[0][4] if return_logprobs else None
                 else:
                     tokens = torch.cat([o[0] for o in outs], 0)
                     logits = torch.cat([o[1] for o in outs], 0) if return_logits else None
                     h, c = torch.cat([o[2] for o in outs], 1), torch.cat([o[3] for o in outs], 1)
+                    logprobs = torch.cat([o[4] for o in outs], 0) if return_logprobs else None
                 state = (h, c)
             else:
                 if N > 0:
                     _ext.fallback(f"char-LM decode (B={B}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
-                tokens, logits, state = dec.reference(self._step, state, first, N, temperature=temperature, seed=seed,
-                                                      pos0=P, forced=forced, return_logits=return_logits)
+                tokens, logits, state, *rest = dec.reference(self._step, state, first, N, temperature=temperature,
+                                                             seed=seed, pos0=P, forced=forced,
+                                                             return_logits=return_logits, **filt)
+                logprobs = rest[0] if return_logprobs else None
                 if return_logits and logits is None:  # (no position at all)
                     logits = torch.empty(B, 0, V, device=dev)
         finally:
             self._state = kept
             self.train(training)
-        out = (tokens,) + ((logits,) if return_logits else ()) + ((state,) if return_state else ())
+        lengths = None
+        if stop is not None or return_lengths:
+            hit = tokens == stop if stop is not None else torch.zeros_like(tokens, dtype=torch.bool)
+            before = hit.cumsum(dim=1) - hit.to(torch.int64)  # a row's stop tokens before each position
+            lengths = ((before == 0).sum(dim=1)).to(torch.int64)  # up to and including the first
+            if stop is not None:
+                tokens = torch.where(before > 0, torch.full_like(tokens, int(stop)), tokens)
+                if logprobs is not None:
+                    logprobs = torch.where(before > 0, torch.zeros_like(logprobs), logprobs)
+        out = ((tokens,) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
+               + ((lengths,) if return_lengths else ()) + ((state,) if return_state else ()))
         return out[0] if len(out) == 1 else out
 
 
