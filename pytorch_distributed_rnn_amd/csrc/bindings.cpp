@@ -138,6 +138,26 @@ void report_stamps(const char* what, const Tensor& st, int iters) {
   }
   fprintf(stderr, "\n");
 }
+// The persistent large-H recurrence's stamps (PDRNN_TUNE persist_stamps=1):
+// workgroup 0's s_memtime at 8 points of steps 0..63, `p` = [64][8] copied to
+// the host; mean cycles per phase over steps 8..62 (past the start-up; the
+// next step's start closes the last phase).
+void report_persist_stamps(const char* what, int B, int H, const int64_t* p) {
+  double d[6] = {0, 0, 0, 0, 0, 0}, step = 0;
+  int n = 0;
+  for (int s = 8; s < 63; ++s) {
+    const int64_t* r = p + s * 8;
+    const int64_t* q = p + (s + 1) * 8;
+    if (!r[0] || !q[0]) continue;
+    for (int k = 0; k < 6; ++k) d[k] += (double)(r[k + 1] - r[k]);
+    step += (double)(q[0] - r[0]);
+    ++n;
+  }
+  static const char* names[6] = {"wait", "loads+mfma", "lds partials", "cell+h store", "arrive", "acts/c stores"};
+  fprintf(stderr, "[persist stamps] %s B=%d H=%d: cycles/step %.0f |", what, B, H, n ? step / n : 0.0);
+  for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.0f", names[k], n ? d[k] / n : 0.0);
+  fprintf(stderr, "\n");
+}
 // progress-ordered wave priority in the small-H recurrences (PDRNN_TUNE prio=0 off):
 // B = 1440: 0.403 -> 0.387 ms/step (profiles/r3p_prio.md); rotation every 2^3 step pairs
 int prio_env() {
@@ -1039,7 +1059,6 @@ enum PersistResult { kPersistNotRun = 0, kPersistOk = 1, kPersistFailed = 2 };
 std::atomic<int> g_persist_verify{-1};     // -1: PDRNN_LSTM_PERSIST_VERIFY (default off); 1 launch, 2 step
 std::atomic<int> g_persist_inject{0};      // tests: flag the next N launches as timed out
 std::atomic<long long> g_persist_fallbacks{0};
-std::atomic<long long> g_persist_tagx{0};  // launches on the tagged forward exchange
 // after the first timed-out launch in a process the persistent path is off for
 // good: a lost co-residency (RCCL kernels beside it) tends to recur every step,
 // and each occurrence costs the 2 s spin bound plus the per-step re-run
@@ -1054,18 +1073,35 @@ int persist_verify_mode() {
   return env;
 }
 bool persist_verify_on() { return persist_verify_mode() == 1; }
-// leaked on purpose: no tensor destructor runs after the HIP runtime is gone
-std::vector<Tensor>& persist_sticky() { static auto& v = *new std::vector<Tensor>(64); return v; }
-// host mirrors: raw pinned words, never freed (a pinned tensor held in a
-// static is released by the host caching allocator at exit, after tools such
-// as the profiler have finalised)
 int* pinned_word() {
   void* p = nullptr;
   TORCH_CHECK(hipHostMalloc(&p, sizeof(int), hipHostMallocDefault) == hipSuccess, "hipHostMalloc");
   *static_cast<int*>(p) = 0;
   return static_cast<int*>(p);
 }
-std::vector<int*>& persist_sticky_host() { static auto& v = *new std::vector<int*>(64, nullptr); return v; }
+// A device's state of the persistent path, created on first use and leaked on
+// purpose: no tensor destructor runs after the HIP runtime is gone, and the
+// host words are raw pinned memory, never freed (a pinned tensor held in a
+// static is released by the host caching allocator at exit, after tools such
+// as the profiler have finalised).
+struct PersistDev {
+  Tensor sticky;     // device int32 [1]: set by a timed-out launch, cleared only by the host
+  int* sticky_host;  // its pinned mirror, copied after every launch
+  int* flag;         // pinned: the launch's own err word (verification per launch)
+  int dev;
+};
+// the current device's state; null when it does not exist yet and !create
+PersistDev* persist_dev(bool create) {
+  static auto& devs = *new std::vector<PersistDev*>(64, nullptr);
+  int dev = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice");
+  if (!create && (dev < 0 || dev >= 64)) return nullptr;
+  TORCH_CHECK(dev >= 0 && dev < 64, "device index");
+  if (!devs[dev] && create)
+    devs[dev] = new PersistDev{at::zeros({1}, at::TensorOptions().device(at::kCUDA, dev).dtype(at::kInt)),
+                               pinned_word(), pinned_word(), dev};
+  return devs[dev];
+}
 
 // Row tiles of the persistent recurrence for this launch, or 0 when the
 // per-step kernels run it (PDRNN_LSTM_PERSIST=0, an explicit tile, the path
@@ -1118,70 +1154,53 @@ int* persist_sync_words(int dev, hipStream_t st, int64_t n, const at::TensorOpti
   return r;
 }
 
+// One persistent launch: plan, sync words, launch, verify (the three modes
+// above).
 int large_persist(const PdrnnLstmLargeStepArgs& a, int ndir, bool backward, int dt, int64_t tile,
                   const at::TensorOptions& opts, hipStream_t st) {
   static const bool check = [] {
     const char* e = std::getenv("PDRNN_LSTM_PERSIST_CHECK");
     return e && std::atoi(e) != 0;
   }();
-  const int mode = 0;  // kernel mode bits: 16 = test hook (persist_inject_timeouts)
   const int mt = large_persist_plan(a.B, a.H, ndir, backward, dt, tile);
   if (mt == 0) return kPersistNotRun;
-  int dev = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice");
-  const int nmb = (a.B + 16 * mt - 1) / (16 * mt);
-  std::vector<Tensor>& sticky = persist_sticky();
-  std::vector<int*>& sticky_host = persist_sticky_host();
-  TORCH_CHECK(dev >= 0 && dev < 64, "device index");
-  if (!sticky[dev].defined()) {
-    sticky[dev] = at::zeros({1}, opts.dtype(at::kInt));
-    sticky_host[dev] = pinned_word();
-  }
-  if (__atomic_load_n(sticky_host[dev], __ATOMIC_RELAXED) != 0) {
+  PersistDev& pd = *persist_dev(true);
+  if (__atomic_load_n(pd.sticky_host, __ATOMIC_RELAXED) != 0) {
     // per-step verification: an earlier launch of this step timed out -- the
     // step's check re-runs it; the rest of the step takes the per-step kernels
     if (persist_verify_mode() == 2) return kPersistNotRun;
     TORCH_CHECK(false, "persistent LSTM recurrence: a grid-sync wait timed out in an earlier launch (results invalid)");
   }
-  // [counters | err | pad | stamps]; PDRNN_TUNE persist_stamps=1: workgroup
-  // 0 records s_memtime at 7 points of steps 0..63 (kernel mode bit 8),
-  // reported per phase after the launch (diagnostics: the launch synchronises)
+  // sync words [counters | err | pad | stamps], zero at launch.  PDRNN_TUNE
+  // persist_stamps=1: workgroup 0 records s_memtime at 7 points of steps
+  // 0..63 (kernel mode 8), reported per phase after the launch (diagnostics:
+  // the launch synchronises)
+  const int nmb = (a.B + 16 * mt - 1) / (16 * mt);
   const bool pstamps = pdrnn_tune_int("persist_stamps", 0) != 0;
-  const int64_t stamp_ints = pstamps ? 2 * 64 * 8 + 2 : 1;
-  // 16-bit forward: the tagged h exchange (lstm_large.hip ps_poll_h), a
-  // zeroed [2][ndir][B][H] dword buffer behind the counters (16-byte aligned)
-  const bool tagx = !backward && dt != 2 && a.T < 65535 && pdrnn_tune_int("persist_tagx", 0) != 0;
-  const int64_t head = (ndir * nmb + 1 + stamp_ints + 2 + 3) & ~(int64_t)3;
-  const int nslots = tagx ? std::max(2, std::min(pdrnn_tune_int("persist_tagx_slots", 2), a.T)) : 0;
-  const int64_t xints = (int64_t)nslots * ndir * a.B * a.H;
+  const int64_t words = ndir * nmb + 1 + (pstamps ? 2 * 64 * 8 + 2 : 1) + 2;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool pooled = !pstamps && !tagx && hipStreamIsCapturing(st, &cap) == hipSuccess &&
-                      cap == hipStreamCaptureStatusNone;
+  const bool pooled = !pstamps && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
   Tensor sync;
-  int* cnt = pooled ? persist_sync_words(dev, st, head, opts) : nullptr;
+  int* cnt = pooled ? persist_sync_words(pd.dev, st, words, opts) : nullptr;
   if (cnt == nullptr) {
-    sync = at::zeros({head + xints}, opts.dtype(at::kInt));
+    sync = at::zeros({words}, opts.dtype(at::kInt));
     cnt = sync.data_ptr<int>();
   }
-  uint32_t* xchg = tagx ? reinterpret_cast<uint32_t*>(cnt + head) : nullptr;
-  int m = mode | (pstamps ? 8 : 0);
+  int* const err = cnt + ndir * nmb;
+  int mode = pstamps ? 8 : 0;
   for (int k = g_persist_inject.load(); k > 0; k = g_persist_inject.load())
-    if (g_persist_inject.compare_exchange_weak(k, k - 1)) { m |= 16; break; }
-  const hipError_t e = pdrnn_lstm_large_persist(&a, ndir, backward ? 1 : 0, dt, mt, cnt, cnt + ndir * nmb,
-                                                sticky[dev].data_ptr<int>(), m, xchg, nslots, st);
+    if (g_persist_inject.compare_exchange_weak(k, k - 1)) { mode |= 16; break; }  // the kernel's test hook
+  const hipError_t e = pdrnn_lstm_large_persist(&a, ndir, backward ? 1 : 0, dt, mt, cnt, err,
+                                                pd.sticky.data_ptr<int>(), mode, st);
   if (e != hipSuccess) {
     (void)hipGetLastError();  // e.g. grid cannot be co-resident: per-step path
     return kPersistNotRun;
   }
-  if (tagx) g_persist_tagx++;
   if (persist_verify_on()) {
-    static std::vector<int*>& flag = *new std::vector<int*>(64, nullptr);
-    if (!flag[dev]) flag[dev] = pinned_word();
-    int* hf = flag[dev];
-    hf[0] = 0;
-    TORCH_CHECK(hipMemcpyAsync(hf, cnt + ndir * nmb, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess, "flag copy");
+    pd.flag[0] = 0;
+    TORCH_CHECK(hipMemcpyAsync(pd.flag, err, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess, "flag copy");
     TORCH_CHECK(hipStreamSynchronize(st) == hipSuccess, "persistent LSTM: stream synchronisation failed");
-    if (hf[0] != 0) {
+    if (pd.flag[0] != 0) {
       g_persist_fallbacks++;
       const bool keep = std::getenv("PDRNN_LSTM_PERSIST_RETRY") != nullptr;  // tests: keep retrying
       if (!keep) g_persist_disabled = 1;
@@ -1189,39 +1208,24 @@ int large_persist(const PdrnnLstmLargeStepArgs& a, int ndir, bool backward, int 
                    "lost, fallback #%lld); re-running the layer on the per-step kernels%s\n",
                    backward ? "backward" : "forward", (long long)g_persist_fallbacks.load(),
                    keep ? "" : " and using them for the rest of the process");
-      TORCH_CHECK(hipMemsetAsync(sticky[dev].data_ptr<int>(), 0, sizeof(int), st) == hipSuccess, "sticky reset");
+      TORCH_CHECK(hipMemsetAsync(pd.sticky.data_ptr<int>(), 0, sizeof(int), st) == hipSuccess, "sticky reset");
       return kPersistFailed;
     }
   }
-  TORCH_CHECK(hipMemcpyAsync(sticky_host[dev], sticky[dev].data_ptr<int>(), sizeof(int), hipMemcpyDeviceToHost, st) ==
+  TORCH_CHECK(hipMemcpyAsync(pd.sticky_host, pd.sticky.data_ptr<int>(), sizeof(int), hipMemcpyDeviceToHost, st) ==
                   hipSuccess, "sticky copy");
   if (pstamps) {
     // the kernel's stamp base: (err + 1) rounded up to 8 bytes (lstm_large.hip pdrnn_lstm_large_persist)
-    const uintptr_t base = (reinterpret_cast<uintptr_t>(cnt + ndir * nmb + 1) + 7) & ~(uintptr_t)7;
-    const int64_t off = (int64_t)(base - reinterpret_cast<uintptr_t>(sync.data_ptr<int>())) / 4;
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(err + 1) + 7) & ~(uintptr_t)7;
+    const int64_t off = (int64_t)(base - reinterpret_cast<uintptr_t>(cnt)) / 4;
     auto h = sync.narrow(0, off, 2 * 64 * 8).cpu();
-    const int64_t* p = reinterpret_cast<const int64_t*>(h.data_ptr<int>());
-    double d[6] = {0, 0, 0, 0, 0, 0}, step = 0;
-    int n = 0;
-    for (int s = 8; s < 63; ++s) {  // (steps 8..62: past the start-up, the next step's start closes the last phase)
-      const int64_t* r = p + s * 8;
-      const int64_t* q = p + (s + 1) * 8;
-      if (!r[0] || !q[0]) continue;
-      for (int k = 0; k < 6; ++k) d[k] += (double)(r[k + 1] - r[k]);
-      step += (double)(q[0] - r[0]);
-      ++n;
-    }
-    static const char* names[6] = {"wait", "loads+mfma", "lds partials", "cell+h store", "arrive", "acts/c stores"};
-    fprintf(stderr, "[persist stamps] %s B=%d H=%d: cycles/step %.0f |", backward ? "bwd" : "fwd", a.B, a.H,
-            n ? step / n : 0.0);
-    for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.0f", names[k], n ? d[k] / n : 0.0);
-    fprintf(stderr, "\n");
+    report_persist_stamps(backward ? "bwd" : "fwd", a.B, a.H, reinterpret_cast<const int64_t*>(h.data_ptr<int>()));
   }
   if (check && persist_verify_mode() != 2) {  // per-step verification re-runs the step instead
-    int err = 0;  // (the flag may live in the pooled sync words: read it through the pointer)
-    TORCH_CHECK(hipMemcpyAsync(&err, cnt + ndir * nmb, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+    int flag = 0;  // (the flag may live in the pooled sync words: read it through the pointer)
+    TORCH_CHECK(hipMemcpyAsync(&flag, err, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
                     hipStreamSynchronize(st) == hipSuccess, "persistent LSTM: flag read failed");
-    TORCH_CHECK(err == 0, "persistent LSTM grid sync timed out");
+    TORCH_CHECK(flag == 0, "persistent LSTM grid sync timed out");
   }
   return kPersistOk;
 }
@@ -1229,37 +1233,21 @@ int large_persist(const PdrnnLstmLargeStepArgs& a, int ndir, bool backward, int 
 // The current device's sticky timeout flag (device int32 [1], created on
 // first use): the deferred per-step verification all-reduces it across ranks
 // and hands it to the optimizer launch as its skip word.
-Tensor persist_sticky_flag() {
-  int dev = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice");
-  TORCH_CHECK(dev >= 0 && dev < 64, "device index");
-  std::vector<Tensor>& sticky = persist_sticky();
-  if (!sticky[dev].defined()) {
-    sticky[dev] = at::zeros({1}, at::TensorOptions().device(at::kCUDA, dev).dtype(at::kInt));
-    persist_sticky_host()[dev] = pinned_word();
-  }
-  return sticky[dev];
-}
+Tensor persist_sticky_flag() { return persist_dev(true)->sticky; }
 
 // Row-owning fp32 recurrence at H = 128 (kernels/lstm_rows_f32.hip) instead of
 // the per-step / persistent kernels; PDRNN_TUNE rows=0 turns it off (A/B).
-bool rows_f32_on() {
-  static const bool on = [] {
-    return pdrnn_tune_int("rows", 1) != 0;
-  }();
-  return on;
-}
+bool rows_f32_on() { return pdrnn_tune_int("rows", 1) != 0; }
 
 // Per-step verification: true when a persistent launch on this device timed
 // out since the last check (synchronises); the flag is cleared, the timeout
 // counted, and the persistent path turned off for the process.
 bool persist_step_check() {
-  int dev = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice");
-  if (dev < 0 || dev >= 64 || !persist_sticky()[dev].defined()) return false;
-  if (persist_sticky()[dev].item<int>() == 0) return false;  // synchronises
-  persist_sticky()[dev].zero_();
-  if (persist_sticky_host()[dev]) __atomic_store_n(persist_sticky_host()[dev], 0, __ATOMIC_RELAXED);
+  PersistDev* pd = persist_dev(false);
+  if (pd == nullptr) return false;
+  if (pd->sticky.item<int>() == 0) return false;  // synchronises
+  pd->sticky.zero_();
+  __atomic_store_n(pd->sticky_host, 0, __ATOMIC_RELAXED);
   g_persist_fallbacks++;
   if (std::getenv("PDRNN_LSTM_PERSIST_RETRY") == nullptr) g_persist_disabled = 1;
   std::fprintf(stderr, "[pdrnn] persistent LSTM recurrence: a grid-sync wait timed out in this step (fallback #%lld); "
@@ -1270,10 +1258,9 @@ bool persist_step_check() {
 // End-of-epoch check of the deferred (verify-off) path: raises if any
 // persistent launch on this device timed out since the last check.
 void persist_check() {
-  int dev = 0;
-  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice");
-  if (dev < 0 || dev >= 64 || !persist_sticky()[dev].defined()) return;
-  const int v = persist_sticky()[dev].item<int>();  // synchronises
+  PersistDev* pd = persist_dev(false);
+  if (pd == nullptr) return;
+  const int v = pd->sticky.item<int>();  // synchronises
   TORCH_CHECK(v == 0, "persistent LSTM recurrence: a grid-sync wait timed out (results of that step invalid)");
 }
 
@@ -2109,8 +2096,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-step verification: True when a persistent launch timed out since the last check (synchronises)");
   m.def("persist_inject_timeouts", [](int64_t n) { g_persist_inject = (int)n; },
         "tests: flag the next n persistent launches as timed out");
-  m.def("persist_tagx_launches", []() { return (int64_t)g_persist_tagx.load(); },
-        "persistent forward launches that used the tagged h exchange (PDRNN_TUNE persist_tagx)");
   m.def("persist_fallbacks", []() { return (int64_t)g_persist_fallbacks.load(); },
         "persistent launches re-run on the per-step kernels after a timeout");
   m.def("persist_verify_on", []() { return persist_verify_mode() != 0; },

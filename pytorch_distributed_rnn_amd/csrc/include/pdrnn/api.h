@@ -369,16 +369,10 @@ hipError_t pdrnn_lstm_large_step(const PdrnnLstmLargeStepArgs* a, int ndir, int 
 hipError_t pdrnn_lstm_large_bwd_first(const PdrnnLstmLargeStepArgs* a, int ndir, int dtype, hipStream_t stream);
 // Row-owning fp32 recurrence (kernels/lstm_rows_f32.hip): one launch per layer
 // pass, 16 batch rows and all of W_hh per workgroup, no grid sync; H = 128,
-// fp32 storage.  The backward needs pdrnn_lstm_large_bwd_first first.
+// fp32 storage.  The backward runs the first processed step's cell backward
+// itself (from dhn / dcn): no pdrnn_lstm_large_bwd_first launch before it.
 int pdrnn_lstm_rows_f32_supported(int H, int dtype);
 hipError_t pdrnn_lstm_rows_f32(const PdrnnLstmLargeStepArgs* a, int ndir, int backward, hipStream_t stream);
-// Persistent recurrence: all T steps of a layer in one launch (occupancy-checked, all workgroups co-resident) with
-// W_hh register-resident.  persist_mt: rows-per-workgroup / 16 for this shape
-// (0 = not covered); counters: ndir * ceil(B / (16 mt)) zeroed ints; err: an
-// int set to 1 if a grid-sync spin timed out (sticky, if not null: also set,
-// never cleared); mode: 0 (diagnostic bits, see the kernel); xchg: null, or for a
-// 16-bit forward nslots (>= 2) * ndir * B * H zeroed dwords (16-byte aligned): the tagged
-// h exchange instead of the arrival counters (lstm_large.hip ps_poll_h).
 // Weight-shadow pack (kernels/shadow_pack.hip): up to PDRNN_PACK_MAX_JOBS
 // 3-D strided gathers dst[i0,i1,i2] = src[...] (+ src2[...]) from bf16 /
 // fp16 / fp32 sources (sdtype), converted to dtype, one launch.  Strides
@@ -402,10 +396,16 @@ typedef struct PdrnnPackBatch {
 } PdrnnPackBatch;
 int64_t pdrnn_shadow_pack_tiles(const PdrnnPackJob* j);
 hipError_t pdrnn_shadow_pack(PdrnnPackBatch* b, hipStream_t stream);
+// Persistent recurrence: all T steps of a layer in one launch (occupancy-checked, all workgroups co-resident) with
+// W_hh register-resident.  persist_mt: rows-per-workgroup / 16 for this shape
+// (0 = not covered); counters: ndir * ceil(B / (16 mt)) zeroed ints; err: an
+// int set to 1 if a grid-sync spin timed out (sticky, if not null: also set,
+// never cleared), followed by the 8-byte aligned stamp words when mode has
+// bit 8; mode: 0, 8 = workgroup 0 records cycle stamps of steps 0..63, 16 =
+// flag the launch as timed out (tests of the host's recovery).
 int pdrnn_lstm_large_persist_mt(int B, int H, int ndir, int dtype, int cus);
 hipError_t pdrnn_lstm_large_persist(const PdrnnLstmLargeStepArgs* a, int ndir, int backward, int dtype, int mt,
-                                    int* counters, int* err, int* sticky, int mode, uint32_t* xchg,
-                                    int nslots, hipStream_t stream);
+                                    int* counters, int* err, int* sticky, int mode, hipStream_t stream);
 // Time-batched GEMM of the large-H layers (kernels/gemm.hip), 16-bit inputs:
 //   C[M, N] (= or +=) sum over the K segments of op(A) op(B) (+ bias[n])
 // A: a_kmajor ? element (m, k) at A[k * lda + m] : A[m * lda + k]

@@ -9,12 +9,16 @@
 //     computes h_{t-1} W_hh^T (v_mfma_f32_16x16x32_{bf16,f16}, LDS
 //     double-buffered, register-staged tiles) and applies the LSTM cell in the
 //     epilogue: the 4 gates of a hidden unit sit in 4 adjacent output columns
-//     (gate-interleaved weight rows) = one DPP quad of the MFMA C layout, so
-//     the gate exchange is 16 quad broadcasts, no LDS round trip;
+//     (gate-interleaved weight rows); the C tile is parked as fp32 in the
+//     idle staging ring (park_tile) and every thread then owns 8 consecutive
+//     columns = 2 units x 4 gates of one row, with 16-byte accesses;
 //   * the BPTT mirror: each reverse step is one MFMA kernel computing
-//     dh_{t-1} = dgates_t W_hh (K = 4H) whose epilogue runs the cell backward
-//     of step t-1 (per-element, no exchange) and emits dgates_{t-1};
-//     weight gradients are then library GEMMs over all timesteps.
+//     dh_{t-1} = dgates_t W_hh (K = 4H) whose epilogue, through the same
+//     parked tile, runs the cell backward of 8 units of step t-1 per thread
+//     and emits dgates_{t-1}; weight gradients are then library GEMMs over
+//     all timesteps.
+// The cell arithmetic itself is pdrnn/large_cell.h (cell_fwd / cell_bwd),
+// shared by every kernel here and in lstm_rows_f32.hip.
 // Both directions of a bidirectional layer run in the same launch
 // (blockIdx.z = direction), doubling the workgroups per step.
 // The same kernels serve the large-H GRU (CELL = 1, ops/gru_large.py): its
@@ -32,6 +36,7 @@
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"
 #include "pdrnn/gemm_pp.h"
+#include "pdrnn/large_cell.h"
 
 namespace pdrnn {
 namespace {
@@ -96,20 +101,6 @@ template <class DT>
 __device__ __forceinline__ V8<DT> ld_v8(const typename DT::S* p) { return *reinterpret_cast<const V8<DT>*>(p); }
 template <class DT>
 __device__ __forceinline__ void st_v8(typename DT::S* p, const V8<DT>& v) { *reinterpret_cast<V8<DT>*>(p) = v; }
-
-__device__ __forceinline__ float sigm(float x) { return fast_rcp(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_(float x) {
-  const float e = __expf(-2.f * fabsf(x));
-  return copysignf((1.f - e) * fast_rcp(1.f + e), x);
-}
-__device__ __forceinline__ float qbcast(float v, int q) {
-  switch (q) {
-    case 0: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xF, 0xF, false));
-    case 1: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x55, 0xF, 0xF, false));
-    case 2: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xAA, 0xF, 0xF, false));
-    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xFF, 0xF, 0xF, false));
-  }
-}
 
 // LDS image of a [ROWS x 8 chunks] tile (128 bytes per row): 16-byte chunk c
 // of row r lives at chunk slot (c ^ (r & 7)) -- the XOR swizzle spreads the
@@ -229,10 +220,77 @@ struct GemmPipe {
   X(3, 256, 128, 4, 2, 3)    \
   X(4, 32, 32, 2, 2, 4)
 
+// Epilogues go through LDS: the MFMA C tile of a GemmPipe<.., WN, ..> block
+// is parked as fp32 [BM][LDC] in the (now idle) staging ring, then every
+// thread owns 8 consecutive columns of a row with 16-byte accesses -- instead
+// of 2-byte scattered accesses straight from the MFMA C layout.
+template <class G, int WN, int LDC>
+__device__ __forceinline__ void park_tile(float* cs, const f32x4 (&acc)[G::MT][G::NT]) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wm = wid / WN, wn = wid % WN;
+#pragma unroll
+  for (int i = 0; i < G::MT; ++i)
+#pragma unroll
+    for (int j = 0; j < G::NT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        cs[(wm * G::WTM + i * 16 + (lane >> 4) * 4 + r) * LDC + wn * G::WTN + j * 16 + (lane & 15)] = acc[i][j][r];
+  __syncthreads();
+}
+
 // ---------------------------------------------------------------------------
 // Forward step: gates = h_{t-1} Wp^T + xp_t  ->  (i, f, g, o), c_t, h_t.
 // Columns are gate-interleaved: col = 4 u + q.
 // ---------------------------------------------------------------------------
+// One forward item = 8 consecutive gate columns (2 hidden units x 4 gates) of
+// a row, split like cell_bwd_load8 / cell_bwd_compute8 into a load half (xp,
+// c_prev, the parked z) and a finish half (cell, stores of the activated
+// gates, c and h), so that a kernel puts the loads of several items in flight
+// before the first one is consumed.
+template <class DT>
+struct CellFwdOps8 {
+  V8<DT> xv;
+  float2 cp;
+  float4 za, zb;
+};
+
+// xp: the row's xp at its first column; cprev + bu: its c_prev at the first
+// unit (cprev null: zeros; tested on the workgroup-uniform base, a scalar
+// branch); z: its parked tile slice
+template <class DT>
+__device__ __forceinline__ void cell_fwd_load8(const typename DT::S* xp, const float* cprev, int64_t bu, const float* z,
+                                               CellFwdOps8<DT>& o) {
+  o.xv = ld_v8<DT>(xp);
+  o.cp = cprev ? *reinterpret_cast<const float2*>(cprev + bu) : make_float2(0.f, 0.f);
+  o.za = *reinterpret_cast<const float4*>(z);
+  o.zb = *reinterpret_cast<const float4*>(z + 4);
+}
+
+// acts: the row's saved gates at its first column; cout / hout: c_t / h_t at
+// the first unit
+template <class DT, int CELL>
+__device__ __forceinline__ void cell_fwd_finish8(const CellFwdOps8<DT>& o, typename DT::S* acts, float* cout,
+                                                 typename DT::S* hout) {
+  float g0[4] = {o.za.x + o.xv.get(0), o.za.y + o.xv.get(1), o.za.z + o.xv.get(2), o.za.w + o.xv.get(3)};
+  float g1[4] = {o.zb.x + o.xv.get(4), o.zb.y + o.xv.get(5), o.zb.z + o.xv.get(6), o.zb.w + o.xv.get(7)};
+  float s0 = o.cp.x, s1 = o.cp.y;
+  const float h0v = cell_fwd<CELL>(g0, s0);
+  const float h1v = cell_fwd<CELL>(g1, s1);
+  V8<DT> av;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    av.set(k, g0[k]);
+    av.set(4 + k, g1[k]);
+  }
+  st_v8<DT>(acts, av);
+  *reinterpret_cast<float2*>(cout) = make_float2(s0, s1);
+  if constexpr (sizeof(typename DT::S) == 2) {
+    *reinterpret_cast<uint32_t*>(hout) = (uint32_t)DT::from_f(h0v) | ((uint32_t)DT::from_f(h1v) << 16);
+  } else {
+    *reinterpret_cast<float2*>(hout) = make_float2(h0v, h1v);
+  }
+}
+
 // CELL 1 = GRU on the same quad (host packing in ops/gru_large.py): the four
 // columns of a unit are [r | z | n_x | n_h] (n_x = W_in x + b_in from xp,
 // n_h = W_hn h + b_hn), cseq holds the fp32 hidden state h_t, and the saved
@@ -263,26 +321,12 @@ __global__ void __launch_bounds__(WM * WN * 64) lstm_large_fwd_step_kernel(Pdrnn
     G::run(hA, lda, static_cast<const S*>(d.w), H, B, H, m0, n0, smem, acc);
   }
 
-  // Epilogue through LDS: the C tile is parked as fp32 [BM][BN+4] in the
-  // (now idle) staging ring, then every thread owns 8 consecutive columns
-  // (= 2 hidden units x 4 gates) of a row: 16-byte loads of xp, 16-byte
-  // stores of the activated gates, 8-byte c and 4-byte h -- instead of
-  // 2-byte scattered accesses straight from the MFMA C layout.
+  // Epilogue through LDS (park_tile): 16-byte loads of xp, 16-byte stores of
+  // the activated gates, 8-byte c and 4-byte h.
   constexpr int LDC = BN + 4;
   static_assert(BM * LDC * 4 <= G::LDS_ELEMS * sizeof(S), "C tile must fit in the staging ring");
   float* cs = reinterpret_cast<float*>(smem_raw);
-  {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-#pragma unroll
-    for (int i = 0; i < G::MT; ++i)
-#pragma unroll
-      for (int j = 0; j < G::NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          cs[(wm * G::WTM + i * 16 + (lane >> 4) * 4 + r) * LDC + wn * G::WTN + j * 16 + (lane & 15)] = acc[i][j][r];
-  }
-  __syncthreads();
+  park_tile<G, WN, LDC>(cs, acc);
   const S* xp = static_cast<const S*>(d.xp) + (int64_t)t * d.xp_st;
   const float* cprev = first ? d.c0 : d.cseq + (int64_t)tp * B * H;
   float* cout = d.cseq + (int64_t)t * B * H;
@@ -295,62 +339,28 @@ __global__ void __launch_bounds__(WM * WN * 64) lstm_large_fwd_step_kernel(Pdrnn
   // workgroup per CU the epilogue is not hidden behind another workgroup's
   // MFMA loop).
   constexpr int ITEMS = (BM * C8 + G::NTHREADS - 1) / G::NTHREADS;
-  V8<DT> xv[ITEMS];
-  float2 cpv[ITEMS];
-  float4 za[ITEMS], zb[ITEMS];
+  CellFwdOps8<DT> ops[ITEMS];
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) {
     const int e = min((int)threadIdx.x + it * G::NTHREADS, BM * C8 - 1);
     const int row = e / C8, c8 = e - row * C8;
     const int b = min(m0 + row, B - 1);
     const int col = n0 + c8 * 8;
-    xv[it] = ld_v8<DT>(xp + (int64_t)b * d.xp_sb + col);
-    cpv[it] = cprev ? *reinterpret_cast<const float2*>(cprev + (int64_t)b * H + (col >> 2)) : make_float2(0.f, 0.f);
-    za[it] = *reinterpret_cast<const float4*>(cs + row * LDC + c8 * 8);
-    zb[it] = *reinterpret_cast<const float4*>(cs + row * LDC + c8 * 8 + 4);
+    cell_fwd_load8<DT>(xp + (int64_t)b * d.xp_sb + col, cprev, (int64_t)b * H + (col >> 2), cs + row * LDC + c8 * 8,
+                       ops[it]);
   }
+  // (with one item per thread the compiler would otherwise sink the loads
+  // into the guarded block below, behind its scalar loads)
+  asm volatile("" ::: "memory");
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) {
     const int e = threadIdx.x + it * G::NTHREADS;
     const int row = e / C8, c8 = e - row * C8;
     const int b = m0 + row;
     if (e >= BM * C8 || b >= B) continue;
-    const int col = n0 + c8 * 8;
-    const float z[8] = {za[it].x, za[it].y, za[it].z, za[it].w, zb[it].x, zb[it].y, zb[it].z, zb[it].w};
-    float g[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float zz = z[k] + xv[it].get(k);
-      if constexpr (CELL == 0) g[k] = (k & 3) == 2 ? tanh_(zz) : sigm(zz);
-      else g[k] = (k & 3) < 2 ? sigm(zz) : zz;  // GRU: r, z activated; n_x, n_h linear
-    }
-    const int u = col >> 2;
-    const float2 cp = cpv[it];
-    float s0, s1, h0v, h1v;
-    if constexpr (CELL == 0) {
-      s0 = fmaf(g[1], cp.x, g[0] * g[2]);
-      s1 = fmaf(g[5], cp.y, g[4] * g[6]);
-      h0v = g[3] * tanh_(s0);
-      h1v = g[7] * tanh_(s1);
-    } else {
-      // n = tanh(n_x + r n_h) takes n_x's slot in the saved quad;
-      // h = n + z (h_prev - n) with the fp32 h_prev
-      g[2] = tanh_(fmaf(g[0], g[3], g[2]));
-      g[6] = tanh_(fmaf(g[4], g[7], g[6]));
-      s0 = h0v = fmaf(g[1], cp.x - g[2], g[2]);
-      s1 = h1v = fmaf(g[5], cp.y - g[6], g[6]);
-    }
-    V8<DT> av;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) av.set(k, g[k]);
-    st_v8<DT>(acts + (int64_t)b * 4 * H + col, av);
-    *reinterpret_cast<float2*>(cout + (int64_t)b * H + u) = make_float2(s0, s1);
-    if constexpr (sizeof(S) == 2) {
-      const uint32_t hv = (uint32_t)DT::from_f(h0v) | ((uint32_t)DT::from_f(h1v) << 16);
-      *reinterpret_cast<uint32_t*>(hout + (int64_t)b * d.hseq_sb + u) = hv;
-    } else {
-      *reinterpret_cast<float2*>(hout + (int64_t)b * d.hseq_sb + u) = make_float2(h0v, h1v);
-    }
+    const int col = n0 + c8 * 8, u = col >> 2;
+    cell_fwd_finish8<DT, CELL>(ops[it], acts + (int64_t)b * 4 * H + col, cout + (int64_t)b * H + u,
+                               hout + (int64_t)b * d.hseq_sb + u);
   }
 }
 
@@ -358,7 +368,7 @@ __global__ void __launch_bounds__(WM * WN * 64) lstm_large_fwd_step_kernel(Pdrnn
 // step GEMM and the carry of the step after tn (LSTM: dc; GRU: the direct
 // path dh_{tn+1} z_{tn+1}): emits dgates_tn and the new carry; after the
 // first forward step (cell == false) it emits dh0 / dc0 instead.
-template <class DT, int CELL, bool COH = false>
+template <class DT, int CELL>
 __device__ __forceinline__ void cell_bwd_elem(const PdrnnLstmLargeDir& d, int B, int H, int T, bool rev, int tn,
                                               bool cell, int b, int u, float dh, float carry) {
   const int64_t bu = (int64_t)b * H + u;
@@ -376,45 +386,16 @@ __device__ __forceinline__ void cell_bwd_elem(const PdrnnLstmLargeDir& d, int B,
   const bool has_prev = rev ? tpp < T : tpp >= 0;
   // LSTM: c_{tn-1};  GRU: h_{tn-1} (both fp32 in cseq, c0 = initial state)
   const float sp = has_prev ? d.cseq[(int64_t)tpp * B * H + bu] : (d.c0 ? d.c0[bu] : 0.f);
-  struct { S x, y, z, w; } dg;
-  float next;
-  if constexpr (CELL == 0) {
-    const float ig = a0, fg = a1, gg = a2, og = a3;
-    const float tc = tanh_(d.cseq[(int64_t)tn * B * H + bu]);
-    const float dc = fmaf(dh * og, 1.f - tc * tc, carry);
-    dg.x = DT::from_f(dc * gg * ig * (1.f - ig));
-    dg.y = DT::from_f(dc * sp * fg * (1.f - fg));
-    dg.z = DT::from_f(dc * ig * (1.f - gg * gg));
-    dg.w = DT::from_f(dh * tc * og * (1.f - og));
-    next = dc * fg;
-  } else {
-    // h = n + z (h_prev - n), n = tanh(n_x + r n_h):
-    // [dr r(1-r) | dz z(1-z) | dpre_n (x side) | dpre_n r (n_h side)]
-    const float r = a0, z = a1, n = a2, nh = a3;
-    const float dpn = dh * (1.f - z) * (1.f - n * n);
-    dg.x = DT::from_f(dpn * nh * r * (1.f - r));
-    dg.y = DT::from_f(dh * (sp - n) * z * (1.f - z));
-    dg.z = DT::from_f(dpn);
-    dg.w = DT::from_f(dpn * r);
-    next = dh * z;
-  }
+  const float cur = CELL == 0 ? d.cseq[(int64_t)tn * B * H + bu] : 0.f;
+  float dg[4];
+  cell_bwd<CELL>(dh, a0, a1, a2, a3, cur, sp, carry, dg);
   // gate-BLOCKED layout (torch's row order): the next step GEMM pairs it with
   // W_hh^T as stored, and the weight-gradient GEMMs land directly in the
   // parameters' layout (no permutation copies)
   S* dgp = static_cast<S*>(d.dgates) + ((int64_t)tn * B + b) * 4 * H + u;
-  if constexpr (COH) {
-    // persistent kernel: read by the other workgroups of the batch block
-    // within the launch (device-coherent stores, see ps_ld16)
-    const __amdgpu_buffer_rsrc_t r = uniform_rsrc(static_cast<S*>(d.dgates) + (int64_t)tn * B * 4 * H);
-    const uint32_t o = (uint32_t)(((int64_t)b * 4 * H + u) * sizeof(S));
-    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, dg.x), r, o, 0, 16);
-    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, dg.y), r, o + H * sizeof(S), 0, 16);
-    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, dg.z), r, o + 2 * H * sizeof(S), 0, 16);
-    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, dg.w), r, o + 3 * H * sizeof(S), 0, 16);
-  } else {
-    dgp[0] = dg.x; dgp[H] = dg.y; dgp[2 * H] = dg.z; dgp[3 * H] = dg.w;
-  }
-  d.dc_carry[bu] = next;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dgp[q * H] = DT::from_f(dg[q]);
+  d.dc_carry[bu] = carry;
 }
 
 // 8-float (2 x 16-byte) row accesses
@@ -428,7 +409,7 @@ __device__ __forceinline__ void st8(float* p, const float (&v)[8]) {
 }
 
 // Cell backward of 8 consecutive units u0 .. u0+7 of row b (u0 % 8 == 0):
-// cell_bwd_elem's math with 16-byte accesses, split into a load phase and a
+// cell_bwd_elem's step with 16-byte accesses, split into a load phase and a
 // compute phase so that the epilogue of the backward step kernel puts the
 // global loads of several items in flight before the first one is consumed.
 template <class DT>
@@ -485,32 +466,18 @@ __device__ __forceinline__ void cell_bwd_compute8(const PdrnnLstmLargeDir& d, in
   // unit k: gates 4k .. 4k+3 of the 32 loaded (V8 q holds units 2q, 2q+1)
   auto act = [&](int e) { return o.av[e >> 3].get(e & 7); };
   alignas(16) S g[4][8];
-  float next[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const float a0 = act(4 * k), a1 = act(4 * k + 1);
-    const float a2 = act(4 * k + 2), a3 = act(4 * k + 3);
-    if constexpr (CELL == 0) {
-      const float tc = tanh_(o.cur[k]);
-      const float dc = fmaf(dh[k] * a3, 1.f - tc * tc, carry[k]);
-      g[0][k] = DT::from_f(dc * a2 * a0 * (1.f - a0));
-      g[1][k] = DT::from_f(dc * o.sp[k] * a1 * (1.f - a1));
-      g[2][k] = DT::from_f(dc * a0 * (1.f - a2 * a2));
-      g[3][k] = DT::from_f(dh[k] * tc * a3 * (1.f - a3));
-      next[k] = dc * a1;
-    } else {
-      const float dpn = dh[k] * (1.f - a1) * (1.f - a2 * a2);
-      g[0][k] = DT::from_f(dpn * a3 * a0 * (1.f - a0));
-      g[1][k] = DT::from_f(dh[k] * (o.sp[k] - a2) * a1 * (1.f - a1));
-      g[2][k] = DT::from_f(dpn);
-      g[3][k] = DT::from_f(dpn * a0);
-      next[k] = dh[k] * a1;
-    }
+    float dg[4];
+    cell_bwd<CELL>(dh[k], act(4 * k), act(4 * k + 1), act(4 * k + 2), act(4 * k + 3), CELL == 0 ? o.cur[k] : 0.f,
+                   o.sp[k], carry[k], dg);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q][k] = DT::from_f(dg[q]);
   }
   S* dgp = static_cast<S*>(d.dgates) + ((int64_t)tn * B + b) * 4 * H + u0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) st_v8<DT>(dgp + q * H, *reinterpret_cast<const V8<DT>*>(g[q]));
-  st8(d.dc_carry + bu, next);
+  st8(d.dc_carry + bu, carry);
 }
 
 // ---------------------------------------------------------------------------
@@ -541,26 +508,13 @@ __global__ void __launch_bounds__(WM * WN * 64) lstm_large_bwd_step_kernel(Pdrnn
   G::run(static_cast<const S*>(d.dgates) + (int64_t)t * B * 4 * H, 4 * H, static_cast<const S*>(d.wt), 4 * H, B,
          4 * H, m0, n0, smem, acc);
 
-  // Epilogue through LDS (as in the forward): the dh tile is parked as fp32
-  // [BM][BN+4] in the idle staging ring, then each thread runs the cell
-  // backward of 8 consecutive units of one row with 16-byte loads / stores
-  // (acts, c, carry, dout, and one store per gate block of dgates) instead of
-  // per-element 2-byte accesses straight from the MFMA C layout.
+  // Epilogue through LDS (park_tile, as in the forward): each thread runs the
+  // cell backward of 8 consecutive units of one row with 16-byte loads /
+  // stores (acts, c, carry, dout, and one store per gate block of dgates).
   constexpr int LDC = BN + 4;
   static_assert(BM * LDC * 4 <= G::LDS_ELEMS * sizeof(S), "C tile must fit in the staging ring");
   float* cs = reinterpret_cast<float*>(smem_raw);
-  {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-#pragma unroll
-    for (int i = 0; i < G::MT; ++i)
-#pragma unroll
-      for (int j = 0; j < G::NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          cs[(wm * G::WTM + i * 16 + (lane >> 4) * 4 + r) * LDC + wn * G::WTN + j * 16 + (lane & 15)] = acc[i][j][r];
-  }
-  __syncthreads();
+  park_tile<G, WN, LDC>(cs, acc);
   constexpr int C8 = BN / 8;
   // items in batches of IB: every item's global operands of a batch are in
   // flight together (see the forward epilogue)
@@ -771,19 +725,15 @@ __global__ void __launch_bounds__(512) lstm_large_fwd_step_pp_kernel(PdrnnLstmLa
     __syncthreads();
 #pragma unroll
   for (int i0 = 0; i0 < ITEMS; i0 += IB) {
-    V8<DT> xv[IB];
-    float2 cpv[IB];
-    float4 za[IB], zb[IB];
+    CellFwdOps8<DT> ops[IB];
 #pragma unroll
     for (int it = 0; it < IB; ++it) {
       const int e = tid + (i0 + it) * 512;
       const int row = e / C8, c8 = e - row * C8;
       const int b = min(m0 + half * 128 + row, B - 1);
       const int col = n0 + c8 * 8;
-      xv[it] = ld_v8<DT>(xp + (int64_t)b * d.xp_sb + col);
-      cpv[it] = cprev ? *reinterpret_cast<const float2*>(cprev + (int64_t)b * H + (col >> 2)) : make_float2(0.f, 0.f);
-      za[it] = *reinterpret_cast<const float4*>(cs + row * kPpLdc + c8 * 8);
-      zb[it] = *reinterpret_cast<const float4*>(cs + row * kPpLdc + c8 * 8 + 4);
+      cell_fwd_load8<DT>(xp + (int64_t)b * d.xp_sb + col, cprev, (int64_t)b * H + (col >> 2),
+                         cs + row * kPpLdc + c8 * 8, ops[it]);
     }
 #pragma unroll
     for (int it = 0; it < IB; ++it) {
@@ -791,36 +741,9 @@ __global__ void __launch_bounds__(512) lstm_large_fwd_step_pp_kernel(PdrnnLstmLa
       const int row = e / C8, c8 = e - row * C8;
       const int b = m0 + half * 128 + row;
       if (b >= B) continue;
-      const int col = n0 + c8 * 8;
-      const float z[8] = {za[it].x, za[it].y, za[it].z, za[it].w, zb[it].x, zb[it].y, zb[it].z, zb[it].w};
-      float g[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float zz = z[k] + xv[it].get(k);
-        if constexpr (CELL == 0) g[k] = (k & 3) == 2 ? tanh_(zz) : sigm(zz);
-        else g[k] = (k & 3) < 2 ? sigm(zz) : zz;
-      }
-      const int u = col >> 2;
-      const float2 cp = cpv[it];
-      float s0, s1, h0v, h1v;
-      if constexpr (CELL == 0) {
-        s0 = fmaf(g[1], cp.x, g[0] * g[2]);
-        s1 = fmaf(g[5], cp.y, g[4] * g[6]);
-        h0v = g[3] * tanh_(s0);
-        h1v = g[7] * tanh_(s1);
-      } else {
-        g[2] = tanh_(fmaf(g[0], g[3], g[2]));
-        g[6] = tanh_(fmaf(g[4], g[7], g[6]));
-        s0 = h0v = fmaf(g[1], cp.x - g[2], g[2]);
-        s1 = h1v = fmaf(g[5], cp.y - g[6], g[6]);
-      }
-      V8<DT> av;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) av.set(k, g[k]);
-      st_v8<DT>(acts + (int64_t)b * 4 * H + col, av);
-      *reinterpret_cast<float2*>(cout + (int64_t)b * H + u) = make_float2(s0, s1);
-      const uint32_t hv = (uint32_t)DT::from_f(h0v) | ((uint32_t)DT::from_f(h1v) << 16);
-      *reinterpret_cast<uint32_t*>(hout + (int64_t)b * d.hseq_sb + u) = hv;
+      const int col = n0 + c8 * 8, u = col >> 2;
+      cell_fwd_finish8<DT, CELL>(ops[it], acts + (int64_t)b * 4 * H + col, cout + (int64_t)b * H + u,
+                                 hout + (int64_t)b * d.hseq_sb + u);
     }
   }
     __syncthreads();
@@ -867,18 +790,16 @@ __global__ void __launch_bounds__(512) lstm_large_bwd_gemm_pp_kernel(PdrnnLstmLa
 // fp16 build spilled inside the main loop; profiles/r3_pp_step/) and was
 // replaced by the GEMM + cell pair below.  PDRNN_TUNE large_pp=0 opts out,
 // =2 takes it at any legal shape (tests).
-inline bool use_pp_step(int B, int N, int ndir, int dsize, bool backward) {
+inline bool use_pp_step(int B, int N, int ndir) {
   const int env = pdrnn_tune_int("large_pp", 1);
-  if (!env || backward || dsize != 2 || N % 256) return false;
+  if (!env || N % 256) return false;
   if (env == 2) return true;
   return B >= 128 && (int64_t)(N / 256) * ((B + 255) / 256) * ndir >= 256;
 }
 
 template <class DT, int CELL>
-hipError_t launch_step_pp(const PdrnnLstmLargeStepArgs* a, int ndir, bool backward, hipStream_t st) {
-  const int N = backward ? a->H : 4 * a->H;
-  dim3 grid(N / 256, (a->B + 255) / 256, ndir);
-  if (backward) return hipErrorInvalidValue;
+hipError_t launch_step_pp(const PdrnnLstmLargeStepArgs* a, int ndir, hipStream_t st) {
+  dim3 grid(4 * a->H / 256, (a->B + 255) / 256, ndir);
   hipLaunchKernelGGL((lstm_large_fwd_step_pp_kernel<DT, CELL>), grid, dim3(512), kPpLds, st, *a);
   return hipGetLastError();
 }
@@ -949,7 +870,7 @@ hipError_t dispatch_step(const PdrnnLstmLargeStepArgs* a, int ndir, bool backwar
     return hipGetLastError();
   }
   if constexpr (sizeof(typename DT::S) == 2) {
-    if (tile < 0 && use_pp_step(a->B, N, ndir, 2, backward)) return launch_step_pp<DT, CELL>(a, ndir, backward, st);
+    if (tile < 0 && !backward && use_pp_step(a->B, N, ndir)) return launch_step_pp<DT, CELL>(a, ndir, st);
   }
   if (tile < 0 || tile > 4) tile = pick_tile(a->B, N, ndir);
   switch (tile) {
@@ -1009,7 +930,7 @@ hipError_t gemm_nt_dispatch(const void* Av, int64_t lda, const void* Btv, int64_
 //   * forward: gates[16 MT x 128] = h_{t-1} W_slice^T, then the cell of the
 //     block's 16 MT x 32 (row, unit) pairs, one per thread (c stays fp32);
 //   * backward: dh[16 MT x 32] = dgates_t W_hh[:, units], then the cell
-//     backward (cell_bwd_elem above) of the same pairs;
+//     backward of the same pairs;
 //   * grid sync: h_t / dgates_t are written and read with device-coherent
 //     (SC1) buffer accesses; every thread drains its stores (vmcnt 0), the
 //     workgroup barriers, and one thread bumps the arrival counter of its
@@ -1034,20 +955,16 @@ struct PersistSync {
   int* cnt;   // [ndir][NMB] arrival counters, zero at launch
   int* err;   // set to 1 when a spin timed out (this launch: releases every waiter)
   int* sticky;  // also set on a timeout; never cleared (the host checks it)
-  int mode;   // diagnostics (wrong results): bit 0 no waits, bit 1 no step GEMM, bit 2 no store drain,
-              // bit 4 flag the launch as timed out (tests of the host's recovery)
-  long long* stamps;  // mode bit 3: workgroup 0 records s_memtime at 8 points of steps 0..63
-  uint32_t* xchg;     // tagged forward exchange (16-bit types): [nslots][ndir][B][H] dwords, zero
-                      // at launch, or null for the arrival-counter protocol (see ps_poll_h)
-  int nslots;         // exchange ring length (>= 2)
+  int mode;   // 8: record stamps; 16: flag the launch as timed out (tests of the host's recovery)
+  long long* stamps;  // mode 8: workgroup 0 records s_memtime at 8 points of steps 0..63
 };
 #define PS_STAMP(k)                                                                          \
   if ((sync.mode & 8) && blockIdx.x == 0 && threadIdx.x == 0 && s < 64)                      \
     sync.stamps[s * 8 + (k)] = (long long)__builtin_amdgcn_s_memtime();
 
-__device__ __forceinline__ void ps_arrive(int* c, int mode = 0) {
+__device__ __forceinline__ void ps_arrive(int* c) {
   // every wave's device-coherent stores are complete before the count moves
-  if (!(mode & 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1108,79 +1025,15 @@ __device__ __forceinline__ void ps_coords(int NCB, int NMB, int& dir, int& cb, i
   cb = l / NMB;
 }
 
-// Tagged forward exchange (16-bit types; PersistSync::xchg non-null).  The
-// arrival-counter protocol costs a step ~43% of its cycles on the char-LM
-// shape (wait 34% + store drain and count 9%,
-// profiles/r6/persist_fwd_step_cycles.md): every producer drains its h_t
-// stores before counting, and the reader loads h_{t-1} only after it has seen
-// the count.  Here h_t travels as one dword per value -- bf16/f16 bits in the
-// low half, the step tag s + 1 in the high half -- in a ring of nslots >= 2
-// exchange slots [nslots][ndir][B][H], zero at launch.  A reader of step s
-// polls its A-fragment chunks of slot (s - 1) % nslots until every dword
-// carries tag s, so the data IS the flag: no drain, no counter, and the loads
-// that succeed are the operands.  Reusing a slot is safe: a producer writes
-// slot s % nslots again at step s + nslots >= s + 2 only after it has read
-// h_{s+1} of every column block of its batch block, i.e. after all of them
-// finished step s + 1, whose reads of the slot precede their cell phase.
-// Tags are unique within a launch (T < 65535, checked by the host).  The spin
-// is bounded like ps_wait (~2 s, *err releases every other poller).
-// Measured slower than the counters (PDRNN_TUNE persist_tagx, default off;
-// profiles/r6/persist_fwd_step_cycles.md).
-template <int MT, int KS>
-__device__ __forceinline__ void ps_poll_h(uint4 (&af)[MT][KS], const PersistSync& sync, const uint32_t* slot,
-                                          uint32_t want, int mb, int fr, int fq, int k0, int B, int H) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t rx = ps_rsrc(slot);
-  const uint64_t t0 = wall_clock64();
-  // probe: re-reading the whole operand every round (8 KiB a wave, 16 MiB a
-  // grid round on the char-LM shape) congests the device-coherent path and
-  // was 30% slower than the counters; one dword a lane watches the last unit
-  // of producer block (fq mod KS) of its row, and the full load is issued
-  // when every probe shows the tag (re-polled in full if any chunk lags)
-  bool probing = true;
-  for (;;) {
-    bool ok = true;
-    if (probing) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
-        const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(
-            rx, (uint32_t)((row * H + k0 + (fq % KS) * PS_NU + PS_NU - 1) * 4), 0, PS_SC1);
-        ok = ok && (v >> 16) == want;
-      }
-      if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
-        probing = false;
-        continue;
-      }
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const uint32_t off = (uint32_t)((row * H + k0 + ks * 32 + fq * 8) * 4);
-          const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, PS_SC1);
-          const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rx, off + 16, 0, PS_SC1);
-          ok = ok && (lo.x >> 16) == want && (lo.y >> 16) == want && (lo.z >> 16) == want && (lo.w >> 16) == want &&
-               (hi.x >> 16) == want && (hi.y >> 16) == want && (hi.z >> 16) == want && (hi.w >> 16) == want;
-          af[mt][ks] = make_uint4((lo.x & 0xffffu) | (lo.y << 16), (lo.z & 0xffffu) | (lo.w << 16),
-                                  (hi.x & 0xffffu) | (hi.y << 16), (hi.z & 0xffffu) | (hi.w << 16));
-        }
-      }
-      if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-    const int e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sync.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    if (e != 0) break;
-    if (wall_clock64() - t0 > 200000000ull) {  // 100 MHz constant clock: 2 s
-      if ((threadIdx.x & 63) == 0) {
-        __hip_atomic_store(sync.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sync.sticky) __hip_atomic_store(sync.sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      break;
-    }
-  }
-}
+// (Removed, measured slower: a tagged forward exchange -- template parameter
+// TAGX, ps_poll_h -- in which h_t travelled as one dword per value, the
+// bf16/f16 bits plus the step tag, through a ring of exchange slots, and the
+// readers polled the data itself instead of an arrival counter: no store
+// drain, no counter.  The arrival-counter protocol costs a char-LM step ~43%
+// of its cycles (wait 34% + drain and count 9%), but polling the operand
+// through the device-coherent path cost more: 11805-12212 cycles a forward
+// step against 9519, 16.05 ms against 14.93 ms a char-LM step, whatever the
+// ring length; profiles/r6/persist_fwd_step_cycles.md.)
 
 // Per-step epilogue state lives in registers: the cell state c (forward) and
 // the carry (backward) never leave the thread that owns the (row, unit) pair;
@@ -1188,7 +1041,7 @@ __device__ __forceinline__ void ps_poll_h(uint4 (&af)[MT][KS], const PersistSync
 // acts / c / dout) are loaded right after the arrival, so their latency hides
 // behind the wait; only the exchanged stores (h_t / dgates_t) precede the
 // arrival -- the saved activations and c_t are stored after it.
-template <class DT, int CELL, int KS, int MT, bool TAGX>
+template <class DT, int CELL, int KS, int MT>
 __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(PdrnnLstmLargeStepArgs args,
                                                                             PersistSync sync) {
   typedef typename DT::S S;
@@ -1211,9 +1064,6 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(Pdrn
   const int n0 = cb * 4 * PS_NU;        // first gate column (gate-interleaved)
   const int k0 = wid * (H / PS_WAVES);  // this wave's K range
   int* cnt = sync.cnt + dir * NMB + mb;
-  // exchange slot of step s: s mod the ring length, this direction (TAGX)
-  const int ndirs = gridDim.x / (NCB * NMB);
-  auto xslot = [&](int s, int dr) { return sync.xchg + ((int64_t)((s % sync.nslots) * ndirs + dr)) * B * H; };
 
   // W_hh slice as MFMA B fragments, resident for the whole sequence
   uint4 wf[KS][CT];
@@ -1258,9 +1108,8 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(Pdrn
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) xcur[mt] = xpn[mt];
     PS_STAMP(0)
-    if constexpr (!TAGX) {
-      if (s > S0 && !(sync.mode & 1)) ps_wait(cnt, s * NCB, sync.err, sync.sticky);
-    }
+    // (expected: keeps the wait inline in the step loop, not in a cold block at the function's end)
+    if (__builtin_expect(s > S0, 1)) ps_wait(cnt, s * NCB, sync.err, sync.sticky);
     PS_STAMP(1)
 
     f32x4 acc[MT][CT];
@@ -1269,20 +1118,16 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(Pdrn
 #pragma unroll
       for (int j = 0; j < CT; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const S* hA = first ? static_cast<const S*>(d.h0) : static_cast<const S*>(d.hseq) + (int64_t)tp * d.hseq_st;
-    if (hA != nullptr && !(sync.mode & 2)) {
+    if (hA != nullptr) {
       const int64_t lda = first ? H : d.hseq_sb;
       const __amdgpu_buffer_rsrc_t ra = ps_rsrc(hA);
       uint4 af[MT][KS];
-      if (TAGX && s > S0) {
-        ps_poll_h<MT, KS>(af, sync, xslot(s - 1, dir), (uint32_t)s, mb, fr, fq, k0, B, H);
-      } else {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
+      for (int mt = 0; mt < MT; ++mt) {
+        const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
 #pragma unroll
-          for (int ks = 0; ks < KS; ++ks)
-            af[mt][ks] = ps_ld16(ra, (uint32_t)((row * lda + k0 + ks * 4 * DT::EPC + fq * DT::EPC) * sizeof(S)));
-        }
+        for (int ks = 0; ks < KS; ++ks)
+          af[mt][ks] = ps_ld16(ra, (uint32_t)((row * lda + k0 + ks * 4 * DT::EPC + fq * DT::EPC) * sizeof(S)));
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
@@ -1304,47 +1149,26 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(Pdrn
     PS_STAMP(3)
     float gs[MT][4];
     const __amdgpu_buffer_rsrc_t rh = ps_rsrc(static_cast<S*>(d.hseq) + (int64_t)t * d.hseq_st);
-    const __amdgpu_buffer_rsrc_t rxw = ps_rsrc(TAGX ? static_cast<const void*>(xslot(s, dir)) : static_cast<const void*>(sync.cnt));
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const S* xv = reinterpret_cast<const S*>(&xcur[mt]);
       float z[4] = {DT::to_f(xv[0]), DT::to_f(xv[1]), DT::to_f(xv[2]), DT::to_f(xv[3])};
+      float4 p[PS_WAVES];  // all 8 LDS reads in flight before the first addition
 #pragma unroll
-      for (int w = 0; w < PS_WAVES; ++w) {
-        const float4 p = *reinterpret_cast<const float4*>(red + ((w * MT + mt) * 16 + er) * LDR + 4 * eu);
-        z[0] += p.x; z[1] += p.y; z[2] += p.z; z[3] += p.w;
-      }
-      float* g = gs[mt];
+      for (int w = 0; w < PS_WAVES; ++w)
+        p[w] = *reinterpret_cast<const float4*>(red + ((w * MT + mt) * 16 + er) * LDR + 4 * eu);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if constexpr (CELL == 0) g[k] = k == 2 ? tanh_(z[k]) : sigm(z[k]);
-        else g[k] = k < 2 ? sigm(z[k]) : z[k];
-      }
-      float hv;
-      if constexpr (CELL == 0) {
-        cst[mt] = fmaf(g[1], cst[mt], g[0] * g[2]);
-        hv = g[3] * tanh_(cst[mt]);
-      } else {
-        g[2] = tanh_(fmaf(g[0], g[3], g[2]));
-        cst[mt] = hv = fmaf(g[1], cst[mt] - g[2], g[2]);
-      }
+      for (int w = 0; w < PS_WAVES; ++w) { z[0] += p[w].x; z[1] += p[w].y; z[2] += p[w].z; z[3] += p[w].w; }
+      float (&g)[4] = gs[mt];  // the summed pre-activations in, the saved quad out
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] = z[k];
+      const float hv = cell_fwd<CELL>(g, cst[mt]);
       const int b = mb * 16 * MT + mt * 16 + er;
-      if constexpr (TAGX) {
-        // h_t to hseq (read after the launch: a plain store) and, tagged with
-        // s + 1, to this step's exchange slot (read by the next step's polls)
-        if (b < B) {
-          const uint16_t hb = DT::from_f(hv);
-          static_cast<S*>(d.hseq)[(int64_t)t * d.hseq_st + (int64_t)b * d.hseq_sb + u] = hb;
-          __builtin_amdgcn_raw_buffer_store_b32(((uint32_t)(s + 1) << 16) | hb, rxw, (uint32_t)((b * H + u) * 4), 0,
-                                                PS_SC1);
-        }
-      } else {
-        if (b < B) ps_st(rh, (uint32_t)((b * d.hseq_sb + u) * sizeof(S)), DT::from_f(hv));
-      }
+      if (b < B) ps_st(rh, (uint32_t)((b * d.hseq_sb + u) * sizeof(S)), DT::from_f(hv));
     }
     PS_STAMP(4)
-    if (TAGX || s + 1 == T) __syncthreads();  // (LDS reuse only: nobody counts arrivals)
-    else ps_arrive(cnt, sync.mode);
+    if (s + 1 == T) __syncthreads();  // (LDS reuse only: nobody counts arrivals)
+    else ps_arrive(cnt);
     PS_STAMP(5)
     if (s + 1 < S1) load_xp(rev ? t - 1 : t + 1);
 #pragma unroll
@@ -1364,7 +1188,7 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_fwd_kernel(Pdrn
 // Backward: step s consumes dgates_t (t = T-1-s forward order) and runs the
 // cell backward of tn (the step before t), or emits dh0 / dc0 after the
 // first forward step.  dgates_{T-1} and the initial carry come from
-// lstm_large_bwd_first_kernel.  Same cell math as cell_bwd_elem.
+// lstm_large_bwd_first_kernel.
 template <class DT, int CELL, int KS, int MT>
 __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_bwd_kernel(PdrnnLstmLargeStepArgs args,
                                                                             PersistSync sync) {
@@ -1443,7 +1267,7 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_bwd_kernel(Pdrn
     for (int mt = 0; mt < MT; ++mt) { od[mt] = nd[mt]; ocur[mt] = ncur[mt]; osp[mt] = nsp[mt]; oact[mt] = nact[mt]; }
     // dgates_t of the whole batch block: written by every column block (the
     // first one by the separate first-step kernel, ordered by the launch)
-    if (s > S0 && !(sync.mode & 1)) ps_wait(cnt, s * NCB, sync.err, sync.sticky);
+    if (s > S0) ps_wait(cnt, s * NCB, sync.err, sync.sticky);
     f32x4 acc[MT][CT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -1452,24 +1276,22 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_bwd_kernel(Pdrn
     const __amdgpu_buffer_rsrc_t ra = ps_rsrc(static_cast<const S*>(d.dgates) + (int64_t)t * B * 4 * H);
     // K loop in 4 chunks: a chunk's loads are all in flight before its MFMAs
     constexpr int KC = KS >= 4 ? KS / 4 : 1;
-    if (!(sync.mode & 2)) {
 #pragma unroll
-      for (int kc = 0; kc < KS; kc += KC) {
-        uint4 af[MT][KC];
+    for (int kc = 0; kc < KS; kc += KC) {
+      uint4 af[MT][KC];
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
-#pragma unroll
-          for (int k = 0; k < KC; ++k)
-            af[mt][k] = ps_ld16(ra, (uint32_t)((row * 4 * H + k0 + (kc + k) * 4 * DT::EPC + fq * DT::EPC) * sizeof(S)));
-        }
+      for (int mt = 0; mt < MT; ++mt) {
+        const int row = min(mb * 16 * MT + mt * 16 + fr, B - 1);
 #pragma unroll
         for (int k = 0; k < KC; ++k)
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < CT; ++j) acc[mt][j] = DT::mfma(af[mt][k], wf[kc + k][j], acc[mt][j]);
+          af[mt][k] = ps_ld16(ra, (uint32_t)((row * 4 * H + k0 + (kc + k) * 4 * DT::EPC + fq * DT::EPC) * sizeof(S)));
       }
+#pragma unroll
+      for (int k = 0; k < KC; ++k)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int j = 0; j < CT; ++j) acc[mt][j] = DT::mfma(af[mt][k], wf[kc + k][j], acc[mt][j]);
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -1497,33 +1319,16 @@ __global__ void __launch_bounds__(PS_THREADS) lstm_large_persist_bwd_kernel(Pdrn
       dh += od[mt];
       const S* av = reinterpret_cast<const S*>(&oact[mt]);
       const float a0 = DT::to_f(av[0]), a1 = DT::to_f(av[1]), a2 = DT::to_f(av[2]), a3 = DT::to_f(av[3]);
-      float g0, g1, g2, g3;
-      if constexpr (CELL == 0) {
-        const float tc = tanh_(ocur[mt]);
-        const float dc = fmaf(dh * a3, 1.f - tc * tc, carry[mt]);
-        g0 = dc * a2 * a0 * (1.f - a0);
-        g1 = dc * osp[mt] * a1 * (1.f - a1);
-        g2 = dc * a0 * (1.f - a2 * a2);
-        g3 = dh * tc * a3 * (1.f - a3);
-        carry[mt] = dc * a1;
-      } else {
-        const float dpn = dh * (1.f - a1) * (1.f - a2 * a2);
-        g0 = dpn * a3 * a0 * (1.f - a0);
-        g1 = dh * (osp[mt] - a2) * a1 * (1.f - a1);
-        g2 = dpn;
-        g3 = dpn * a0;
-        carry[mt] = dh * a1;
-      }
+      float dg[4];
+      cell_bwd<CELL>(dh, a0, a1, a2, a3, ocur[mt], osp[mt], carry[mt], dg);
       // gate-blocked dgates_tn (read by the batch block's other workgroups
       // at the next step: device-coherent stores)
       const uint32_t o = (uint32_t)(((int64_t)b * 4 * H + u) * sizeof(S));
-      ps_st(rg, o, DT::from_f(g0));
-      ps_st(rg, o + H * sizeof(S), DT::from_f(g1));
-      ps_st(rg, o + 2 * H * sizeof(S), DT::from_f(g2));
-      ps_st(rg, o + 3 * H * sizeof(S), DT::from_f(g3));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ps_st(rg, o + q * H * sizeof(S), DT::from_f(dg[q]));
     }
     if (s + 1 < T) {
-      ps_arrive(cnt, sync.mode);
+      ps_arrive(cnt);
       const int tn2 = rev ? tn + 1 : tn - 1;  // cell-backward step of s + 1
       if (s + 1 < S1 && (rev ? tn2 < T : tn2 >= 0)) load_ops(tn2);
     }
@@ -1582,10 +1387,7 @@ hipError_t persist_launch(const PdrnnLstmLargeStepArgs* a, int ndir, bool backwa
     return hipErrorInvalidValue;
   } else {
     const size_t lds = (size_t)PS_WAVES * MT * 16 * (4 * PS_NU + 4) * 4;
-    static int occ_fwd_tag = -1;
-    if (sy.xchg != nullptr)
-      return persist_go(lstm_large_persist_fwd_kernel<DT, CELL, KSF, MT, true>, grid, lds, st, *a, sy, &occ_fwd_tag);
-    return persist_go(lstm_large_persist_fwd_kernel<DT, CELL, KSF, MT, false>, grid, lds, st, *a, sy, &occ_fwd);
+    return persist_go(lstm_large_persist_fwd_kernel<DT, CELL, KSF, MT>, grid, lds, st, *a, sy, &occ_fwd);
   }
 }
 
@@ -1607,6 +1409,20 @@ hipError_t persist_dispatch(const PdrnnLstmLargeStepArgs* a, int ndir, bool back
     return mt == 1 ? persist_launch<DT, CELL, 1, 2, 8>(a, ndir, backward, sy, st)
                    : persist_launch<DT, CELL, 2, 2, 8>(a, ndir, backward, sy, st);
   }
+}
+
+// The entry points' runtime ids as types: f(DT{}) for the storage type id
+// (0 bf16, 2 fp32, else fp16), f(DT{}, integral_constant<int, CELL>{}) with
+// the cell id (with_cell: an id that is neither 0 nor 1 is an error).
+template <class F>
+hipError_t with_storage(int dtype, F&& f) {
+  if (dtype == 0) return f(BF16{});
+  if (dtype == 2) return f(F32{});
+  return f(F16{});
+}
+template <class F>
+hipError_t with_storage_cell(int dtype, int cell, F&& f) {
+  return with_storage(dtype, [&](auto dt) { return with_cell(cell, [&](auto c) { return f(dt, c); }); });
 }
 
 }  // namespace
@@ -1647,16 +1463,9 @@ int pdrnn_lstm_large_bwd_splitk(int B, int H, int ndir, int* big) {
 hipError_t pdrnn_lstm_large_step(const PdrnnLstmLargeStepArgs* a, int ndir, int backward, int dtype, int tile,
                                  hipStream_t stream) {
   if (!pdrnn_lstm_large_supported(a->H) || ndir < 1 || ndir > 2) return hipErrorInvalidValue;
-  if (a->cell != 0 && a->cell != 1) return hipErrorInvalidValue;
-  const bool bw = backward != 0;
-  if (dtype == 0)
-    return a->cell ? pdrnn::dispatch_step<pdrnn::BF16, 1>(a, ndir, bw, tile, stream)
-                   : pdrnn::dispatch_step<pdrnn::BF16, 0>(a, ndir, bw, tile, stream);
-  if (dtype == 2)
-    return a->cell ? pdrnn::dispatch_step<pdrnn::F32, 1>(a, ndir, bw, tile, stream)
-                   : pdrnn::dispatch_step<pdrnn::F32, 0>(a, ndir, bw, tile, stream);
-  return a->cell ? pdrnn::dispatch_step<pdrnn::F16, 1>(a, ndir, bw, tile, stream)
-                 : pdrnn::dispatch_step<pdrnn::F16, 0>(a, ndir, bw, tile, stream);
+  return pdrnn::with_storage_cell(dtype, a->cell, [&](auto dt, auto c) {
+    return pdrnn::dispatch_step<decltype(dt), decltype(c)::value>(a, ndir, backward != 0, tile, stream);
+  });
 }
 
 // Persistent recurrence (see above): batch rows per workgroup / 16 (1 or 2)
@@ -1673,50 +1482,32 @@ int pdrnn_lstm_large_persist_mt(int B, int H, int ndir, int dtype, int cus) {
 }
 
 hipError_t pdrnn_lstm_large_persist(const PdrnnLstmLargeStepArgs* a, int ndir, int backward, int dtype, int mt,
-                                    int* counters, int* err, int* sticky, int mode, uint32_t* xchg,
-                                    int nslots, hipStream_t stream) {
+                                    int* counters, int* err, int* sticky, int mode, hipStream_t stream) {
   if ((mt != 1 && mt != 2) || dtype < 0 || dtype > 2) return hipErrorInvalidValue;
-  if (xchg != nullptr && (backward || dtype == 2 || a->T >= 65535 || nslots < 2 || (reinterpret_cast<uintptr_t>(xchg) & 15)))
-    return hipErrorInvalidValue;
   if (dtype == 2 ? (a->H != 128 && a->H != 256) : a->H != 1024) return hipErrorInvalidValue;
-  if (a->cell != 0 && a->cell != 1) return hipErrorInvalidValue;
   const pdrnn::PersistSync sy{counters, err, sticky, mode,
-                              reinterpret_cast<long long*>((reinterpret_cast<uintptr_t>(err + 1) + 7) & ~(uintptr_t)7),
-                              xchg, nslots};
-  const bool bw = backward != 0;
-  if (dtype == 0)
-    return a->cell ? pdrnn::persist_dispatch<pdrnn::BF16, 1>(a, ndir, bw, mt, sy, stream)
-                   : pdrnn::persist_dispatch<pdrnn::BF16, 0>(a, ndir, bw, mt, sy, stream);
-  if (dtype == 2)
-    return a->cell ? pdrnn::persist_dispatch<pdrnn::F32, 1>(a, ndir, bw, mt, sy, stream)
-                   : pdrnn::persist_dispatch<pdrnn::F32, 0>(a, ndir, bw, mt, sy, stream);
-  return a->cell ? pdrnn::persist_dispatch<pdrnn::F16, 1>(a, ndir, bw, mt, sy, stream)
-                 : pdrnn::persist_dispatch<pdrnn::F16, 0>(a, ndir, bw, mt, sy, stream);
+                              reinterpret_cast<long long*>((reinterpret_cast<uintptr_t>(err + 1) + 7) & ~(uintptr_t)7)};
+  return pdrnn::with_storage_cell(dtype, a->cell, [&](auto dt, auto c) {
+    return pdrnn::persist_dispatch<decltype(dt), decltype(c)::value>(a, ndir, backward != 0, mt, sy, stream);
+  });
 }
 
 hipError_t pdrnn_lstm_large_bwd_first(const PdrnnLstmLargeStepArgs* a, int ndir, int dtype, hipStream_t stream) {
   const int64_t n = (int64_t)a->B * a->H;
   dim3 grid((unsigned)((n + 255) / 256), 1, ndir);
-  if (a->cell != 0 && a->cell != 1) return hipErrorInvalidValue;
-  if (dtype == 0) {
-    if (a->cell) hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::BF16, 1>), grid, dim3(256), 0, stream, *a);
-    else hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::BF16, 0>), grid, dim3(256), 0, stream, *a);
-  } else if (dtype == 2) {
-    if (a->cell) hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::F32, 1>), grid, dim3(256), 0, stream, *a);
-    else hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::F32, 0>), grid, dim3(256), 0, stream, *a);
-  } else {
-    if (a->cell) hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::F16, 1>), grid, dim3(256), 0, stream, *a);
-    else hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<pdrnn::F16, 0>), grid, dim3(256), 0, stream, *a);
-  }
-  return hipGetLastError();
+  return pdrnn::with_storage_cell(dtype, a->cell, [&](auto dt, auto c) {
+    hipLaunchKernelGGL((pdrnn::lstm_large_bwd_first_kernel<decltype(dt), decltype(c)::value>), grid, dim3(256), 0, stream,
+                       *a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t pdrnn_gemm_nt(const void* A, int64_t lda, const void* Bt, int64_t ldb, float* C, int64_t ldc,
                          int M, int N, int K, int dtype, int tile, hipStream_t stream) {
   if (K % 64 || N % 32) return hipErrorInvalidValue;
-  if (dtype == 0) return pdrnn::gemm_nt_dispatch<pdrnn::BF16>(A, lda, Bt, ldb, C, ldc, M, N, K, tile, stream);
-  if (dtype == 2) return pdrnn::gemm_nt_dispatch<pdrnn::F32>(A, lda, Bt, ldb, C, ldc, M, N, K, tile, stream);
-  return pdrnn::gemm_nt_dispatch<pdrnn::F16>(A, lda, Bt, ldb, C, ldc, M, N, K, tile, stream);
+  return pdrnn::with_storage(dtype, [&](auto dt) {
+    return pdrnn::gemm_nt_dispatch<decltype(dt)>(A, lda, Bt, ldb, C, ldc, M, N, K, tile, stream);
+  });
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 
 #include "pdrnn/api.h"
 #include "pdrnn/common.h"
+#include "pdrnn/large_cell.h"
 
 namespace pdrnn {
 namespace {
@@ -40,10 +41,6 @@ constexpr int RT = RW * 64;       // threads
 constexpr int RLDH = RH + 4;      // h row stride in LDS (floats)
 constexpr int RLDG = 4 * RH + 4;  // dgates row stride in LDS
 constexpr int RLDP = 64 + 4;      // per-wave gate patch row stride
-
-// the activations of the per-step / persistent kernels (common.h)
-__device__ __forceinline__ float r_sigm(float x) { return sigmoidf_fast(x); }
-__device__ __forceinline__ float r_tanh(float x) { return tanhf_fast(x); }
 
 // 4 MFMAs over one 16-byte chunk: MFMA m takes component m of both operands
 __device__ __forceinline__ f32x4 mfma4(const float4& a, const float4& b, f32x4 c) {
@@ -130,21 +127,8 @@ __global__ void __launch_bounds__(RT) lstm_rows_f32_fwd_kernel(PdrnnLstmLargeSte
     for (int i = 0; i < 4; ++i) {
       const int row = (lane >> 4) + 4 * i;
       const float4 p = *reinterpret_cast<const float4*>(&gp[w][row][4 * ul]);
-      float z[4] = {xc[i].x + p.x, xc[i].y + p.y, xc[i].z + p.z, xc[i].w + p.w};
-      float g[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if constexpr (CELL == 0) g[k] = k == 2 ? r_tanh(z[k]) : r_sigm(z[k]);
-        else g[k] = k < 2 ? r_sigm(z[k]) : z[k];
-      }
-      float hv;
-      if constexpr (CELL == 0) {
-        cst[i] = fmaf(g[1], cst[i], g[0] * g[2]);
-        hv = g[3] * r_tanh(cst[i]);
-      } else {
-        g[2] = r_tanh(fmaf(g[0], g[3], g[2]));
-        cst[i] = hv = fmaf(g[1], cst[i] - g[2], g[2]);
-      }
+      float g[4] = {xc[i].x + p.x, xc[i].y + p.y, xc[i].z + p.z, xc[i].w + p.w};
+      const float hv = cell_fwd<CELL>(g, cst[i]);
       hn[row * RLDH + u] = hv;
       const int b = r0 + row;
       if (b < B) {
@@ -211,29 +195,13 @@ __global__ void __launch_bounds__(RT) lstm_rows_f32_bwd_kernel(PdrnnLstmLargeSte
     const int row = 4 * fq + i;
     const int b = r0 + row;
     dh += dd;
-    const float a0 = act.x, a1 = act.y, a2 = act.z, a3 = act.w;
-    float g0, g1, g2, g3;
-    if constexpr (CELL == 0) {
-      const float tc = r_tanh(cc);
-      const float dc = fmaf(dh * a3, 1.f - tc * tc, carry[i]);
-      g0 = dc * a2 * a0 * (1.f - a0);
-      g1 = dc * sp * a1 * (1.f - a1);
-      g2 = dc * a0 * (1.f - a2 * a2);
-      g3 = dh * tc * a3 * (1.f - a3);
-      carry[i] = dc * a1;
-    } else {
-      const float dpn = dh * (1.f - a1) * (1.f - a2 * a2);
-      g0 = dpn * a3 * a0 * (1.f - a0);
-      g1 = dh * (sp - a2) * a1 * (1.f - a1);
-      g2 = dpn;
-      g3 = dpn * a0;
-      carry[i] = dh * a1;
-    }
+    float dg[4];
+    cell_bwd<CELL>(dh, act.x, act.y, act.z, act.w, cc, sp, carry[i], dg);
     float* dr = dn + row * RLDG + u;
-    dr[0] = g0; dr[RH] = g1; dr[2 * RH] = g2; dr[3 * RH] = g3;
+    dr[0] = dg[0]; dr[RH] = dg[1]; dr[2 * RH] = dg[2]; dr[3 * RH] = dg[3];
     if (b < B) {
       float* o = static_cast<float*>(d.dgates) + (int64_t)tn * B * 4 * RH + (int64_t)b * 4 * RH + u;
-      o[0] = g0; o[RH] = g1; o[2 * RH] = g2; o[3 * RH] = g3;
+      o[0] = dg[0]; o[RH] = dg[1]; o[2 * RH] = dg[2]; o[3 * RH] = dg[3];
     }
   };
   // The first processed step (the layer's last forward step) has no
@@ -302,16 +270,13 @@ int pdrnn_lstm_rows_f32_supported(int H, int dtype) { return dtype == 2 && H == 
 // backward).
 hipError_t pdrnn_lstm_rows_f32(const PdrnnLstmLargeStepArgs* a, int ndir, int backward, hipStream_t stream) {
   if (a->H != pdrnn::RH || ndir < 1 || ndir > 2 || a->B < 1 || a->T < 1) return hipErrorInvalidValue;
-  if (a->cell != 0 && a->cell != 1) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((a->B + 15) / 16), (unsigned)ndir);
-  if (backward) {
-    if (a->cell) hipLaunchKernelGGL(pdrnn::lstm_rows_f32_bwd_kernel<1>, grid, dim3(pdrnn::RT), 0, stream, *a);
-    else hipLaunchKernelGGL(pdrnn::lstm_rows_f32_bwd_kernel<0>, grid, dim3(pdrnn::RT), 0, stream, *a);
-  } else {
-    if (a->cell) hipLaunchKernelGGL(pdrnn::lstm_rows_f32_fwd_kernel<1>, grid, dim3(pdrnn::RT), 0, stream, *a);
-    else hipLaunchKernelGGL(pdrnn::lstm_rows_f32_fwd_kernel<0>, grid, dim3(pdrnn::RT), 0, stream, *a);
-  }
-  return hipGetLastError();
+  return pdrnn::with_cell(a->cell, [&](auto c) {
+    constexpr int CELL = decltype(c)::value;
+    if (backward) hipLaunchKernelGGL(pdrnn::lstm_rows_f32_bwd_kernel<CELL>, grid, dim3(pdrnn::RT), 0, stream, *a);
+    else hipLaunchKernelGGL(pdrnn::lstm_rows_f32_fwd_kernel<CELL>, grid, dim3(pdrnn::RT), 0, stream, *a);
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"

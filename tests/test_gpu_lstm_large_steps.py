@@ -20,9 +20,6 @@ retune cannot silently move it onto another kernel.  The reference itself is
 proved against fp64 torch.nn.LSTM / torch.nn.GRU on the CPU
 (test_reference_matches_torch_fp64, not marked gpu).
 
-Not covered: the fp32 H = 128 persistent backward, reachable only with
-PDRNN_TUNE rows=0, which the binding reads once per process.
-
 Worst |kernel - ref| / bound measured on an MI355X when this file was written
 (hseq / acts / dgates are the 16-bit figures: a correctly rounded bf16 store
 alone reaches 2^-8 / (2^-8 + 1e-4) = 0.975; fp32 storage stays below 0.05):
@@ -35,11 +32,12 @@ alone reaches 2^-8 / (2^-8 + 1e-4) = 0.975; fp32 storage stays below 0.05):
     split-K 32x32 x2 / x4 / x8      (2|4|8, 0, 0, no)         0.962 0.068 0.966 0.940 0.008 0.003
     split-K 128x128 x4              (4, 1, 0, no)             0.966 0.083 0.968 0.952 0.017 0.008
     split-K 128x128 x2              (2, 1, 0, no)             0.966 0.121 0.969 0.952 0.025 0.026
-    persistent 16-bit, mt 1 / 2, counters and tagged (yes)    0.965 0.009 0.968 0.952 0.002 0.001
+    persistent 16-bit, mt 1 / 2     (yes)                     0.965 0.009 0.968 0.952 0.002 0.001
     persistent fp32 backward, H 256 (yes)                     0.017 0.020 0.042 0.001 0.002 0.001
+    persistent fp32 backward, H 128 (yes, PDRNN_TUNE rows=0)  0.011 0.014 0.022 0.001 0.001 0.001
     row-owning fp32, H 128          (rows)                    0.011 0.011 0.018 0.002 0.003 0.002
 
-The 246 GPU cases take 4 s together.
+The 238 GPU cases take 4 s together.
 """
 import collections
 
@@ -299,28 +297,27 @@ def test_pingpong_backward_pair(monkeypatch, cell, H, B, ndir, mask, pp_bwd, dt,
 # --- persistent recurrence, 16-bit, H 1024 ---------------------------------
 # B 128: one 16-row tile per workgroup (mt 1; two when CUs are reserved for
 # RCCL, see below); B 200: two, the last block clamped; B 40 bidirectional
-# with direction 1 reversed, always mt 1 with a partial last block.  tagx: the tagged h exchange
-# of the forward instead of the arrival counters.
+# with direction 1 reversed, always mt 1 with a partial last block.
+_P16 = [(128, 1, 0, 1) + row for row in _cover(6)] + [(B, ndir, mask, mt, dt, "full", 6)
+                                                      for B, ndir, mask, mt in ((200, 1, 0, 2), (40, 2, 2, 1))
+                                                      for dt in ("bf16", "fp16")]
+
+
 @gpu
-@pytest.mark.parametrize("B,ndir,mask,mt,dt,variant,T,tagx",
-                         [(128, 1, 0, 1) + row + (0,) for row in _cover(6)] +
-                         [(128, 1, 0, 1, dt, "full", 6, 1) for dt in ("bf16", "fp16")] +
-                         [(B, ndir, mask, mt, dt, "full", 6, tagx) for B, ndir, mask, mt in ((200, 1, 0, 2), (40, 2, 2, 1))
-                          for dt in ("bf16", "fp16") for tagx in (0, 1)])
+@pytest.mark.parametrize("B,ndir,mask,mt,dt,variant,T",  # (ids: the cases keep the names they had beside the removed
+                         # tagged-exchange cases, whose last column was 1 where theirs was 0)
+                         [pytest.param(*r, id="-".join(map(str, r)) + "-0") for r in _P16])
 @pytest.mark.parametrize("cell", [0, 1])
-def test_persistent_16bit(monkeypatch, cell, B, ndir, mask, mt, dt, variant, T, tagx):
+def test_persistent_16bit(cell, B, ndir, mask, mt, dt, variant, T):
     mod = _ext.require()
     H = 1024
-    set_tune(monkeypatch, persist_tagx=str(tagx))
     if B == 128 and mod.rccl_cta_reserve() > 0:
         # 8 batch blocks x 32 column blocks fill all 256 CUs: once a communicator
         # in this process has reserved CUs for RCCL, the planner pairs the blocks
         mt = 2
     assert mod.lstm_large_persist_mt(B, H, ndir, _DT[dt][1]) == mt
     assert _plan(mod, B, H, ndir, dt, -1)[3]
-    before = mod.persist_tagx_launches()
-    _case(f"persistent 16-bit mt {mt}" + (" tagx" if tagx else ""), H, B, T, ndir, mask, dt, cell, -1, variant)
-    assert mod.persist_tagx_launches() == before + tagx
+    _case(f"persistent 16-bit mt {mt}", H, B, T, ndir, mask, dt, cell, -1, variant)
     mod.persist_check()
 
 
@@ -335,13 +332,20 @@ def test_row_owning_fp32(cell, B, T, ndir, mask, variant):
     _case("row-owning fp32", 128, B, T, ndir, mask, "fp32", cell, -1, variant)
 
 
-# --- persistent backward, fp32, H 256 (its forward: the per-step kernels) ----
+# --- persistent backward, fp32, H 256 and H 128 (its forward: the per-step
+# kernels).  H 128 belongs to the row-owning kernels unless PDRNN_TUNE rows=0.
+_P32 = [(256, 7, 1, 1, 4, v) for v in VARIANTS] + [(256, 7, 1, 1, 1, "full"), (256, 300, 2, 2, 3, "full"),
+                                                   (128, 7, 1, 1, 4, "full"), (128, 300, 2, 2, 3, "full")]
+
+
 @gpu
-@pytest.mark.parametrize("B,ndir,mask,T,variant", [(7, 1, 1, 4, v) for v in VARIANTS] + [(7, 1, 1, 1, "full"),
-                                                                                       (300, 2, 2, 3, "full")])
+@pytest.mark.parametrize("H,B,ndir,mask,T,variant",  # (the H 256 rows keep the ids they had before H was a column)
+                         [pytest.param(*r, id="-".join(map(str, r[1:] if r[0] == 256 else r))) for r in _P32])
 @pytest.mark.parametrize("cell", [0, 1])
-def test_persistent_fp32_backward(cell, B, ndir, mask, T, variant):
+def test_persistent_fp32_backward(monkeypatch, cell, H, B, ndir, mask, T, variant):
     mod = _ext.require()
-    assert mod.lstm_large_persist_mt(B, 256, ndir, 2) > 0 and _plan(mod, B, 256, ndir, "fp32", -1)[3]
-    _case("persistent fp32 bwd", 256, B, T, ndir, mask, "fp32", cell, -1, variant)
+    if H == 128:
+        set_tune(monkeypatch, rows="0")
+    assert mod.lstm_large_persist_mt(B, H, ndir, 2) > 0 and _plan(mod, B, H, ndir, "fp32", -1)[3]
+    _case(f"persistent fp32 bwd H {H}", H, B, T, ndir, mask, "fp32", cell, -1, variant)
     mod.persist_check()
