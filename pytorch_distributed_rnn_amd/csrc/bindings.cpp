@@ -1865,6 +1865,129 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
   HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
 }
 
+// Beam search on the decode kernels: G groups of W beams; the buffers are the
+// caller's (ops/decode.py:alloc_beam_buffers), cum / done row 0 filled.
+void lstm_decode_beam(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
+                      const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
+                      const Tensor& c, const Tensor& scratch, const Tensor& first, const Tensor& cum, const Tensor& done,
+                      const Tensor& tokens, const Tensor& parents, const optional<Tensor>& lp,
+                      const optional<Tensor>& logits, const Tensor& hyp, const optional<Tensor>& hyp_lp, int64_t G,
+                      int64_t W, int64_t stop, bool select_launch) {
+  CHECK_HIP_TENSOR(emb);
+  const c10::DeviceGuard guard(emb.device());
+  const int dt = dtype_code(emb);
+  const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
+  TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
+              "lstm_decode_beam: emb [V, E], one w_ih / w_hh / bias per layer");
+  TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
+              "lstm_decode_beam: h [2, L, S, H] in the weights' dtype");
+  const int64_t S = h.size(2), H = h.size(3), N = tokens.dim() == 2 ? tokens.size(1) : 0;
+  TORCH_CHECK(G >= 1 && W >= 1 && G <= 16 && W <= 16 && G * W == S &&
+              pdrnn_lstm_decode_beam_supported((int)G, (int)W, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
+              "lstm_decode_beam: unsupported shape G=", G, " W=", W, " S=", S, " H=", H, " E=", E, " V=", V, " L=", L,
+              " N=", N);
+  TORCH_CHECK(stop >= -1 && stop < V, "lstm_decode_beam: stop in [0, V), or -1 for none");
+  auto aligned = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  auto f32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
+  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
+  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+  auto sn = [&](const Tensor& t) { return t.dim() == 2 && t.size(0) == S && t.size(1) == N; };
+  std::vector<const void*> pi(L), ph(L);
+  std::vector<const float*> pb(L);
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t I = l == 0 ? E : H;
+    TORCH_CHECK(w_ih[l].is_cuda() && w_ih[l].is_contiguous() && dtype_code(w_ih[l]) == dt && w_ih[l].dim() == 2 &&
+                w_ih[l].size(0) == 4 * H && w_ih[l].size(1) == I && aligned(w_ih[l]), "lstm_decode_beam: w_ih [4H, I]");
+    TORCH_CHECK(w_hh[l].is_cuda() && w_hh[l].is_contiguous() && dtype_code(w_hh[l]) == dt && w_hh[l].dim() == 2 &&
+                w_hh[l].size(0) == 4 * H && w_hh[l].size(1) == H && aligned(w_hh[l]), "lstm_decode_beam: w_hh [4H, H]");
+    TORCH_CHECK(f32(bias[l]) && bias[l].numel() == 4 * H, "lstm_decode_beam: bias [4H] fp32");
+    pi[l] = w_ih[l].data_ptr();
+    ph[l] = w_hh[l].data_ptr();
+    pb[l] = bias[l].data_ptr<float>();
+  }
+  TORCH_CHECK(w_fc.is_cuda() && w_fc.is_contiguous() && dtype_code(w_fc) == dt && w_fc.dim() == 2 && w_fc.size(0) == V &&
+              w_fc.size(1) == H && aligned(w_fc) && aligned(emb) && aligned(h), "lstm_decode_beam: w_fc [V, H]");
+  if (present(b_fc)) TORCH_CHECK(f32(*b_fc) && b_fc->numel() == V, "lstm_decode_beam: b_fc [V] fp32");
+  TORCH_CHECK(f32(c) && c.numel() == L * S * H, "lstm_decode_beam: c [L, S, H] fp32");
+  TORCH_CHECK(f32(scratch) && scratch.numel() == S * V, "lstm_decode_beam: scratch [S, V] fp32");
+  TORCH_CHECK(i64(first) && first.numel() == S, "lstm_decode_beam: first [S] int64");
+  TORCH_CHECK(f32(cum) && cum.dim() == 2 && cum.size(0) == N + 1 && cum.size(1) == S, "lstm_decode_beam: cum [N + 1, S] fp32");
+  TORCH_CHECK(i32(done) && done.dim() == 2 && done.size(0) == N + 1 && done.size(1) == S,
+              "lstm_decode_beam: done [N + 1, S] int32");
+  TORCH_CHECK(i64(tokens) && sn(tokens) && i64(hyp) && sn(hyp), "lstm_decode_beam: tokens / hyp [S, N] int64");
+  TORCH_CHECK(i32(parents) && sn(parents), "lstm_decode_beam: parents [S, N] int32");
+  for (const optional<Tensor>* o : {&lp, &hyp_lp})
+    if (present(*o)) TORCH_CHECK(f32(**o) && sn(**o), "lstm_decode_beam: lp / hyp_lp [S, N] fp32");
+  TORCH_CHECK(!present(hyp_lp) || present(lp), "lstm_decode_beam: hyp_lp needs lp");
+  if (present(logits)) TORCH_CHECK(f32(*logits) && logits->numel() == S * N * V, "lstm_decode_beam: logits [S, N, V] fp32");
+  PdrnnLstmDecodeBeamArgs a{};
+  a.emb = emb.data_ptr();
+  a.w_ih = pi.data();
+  a.w_hh = ph.data();
+  a.bias = pb.data();
+  a.w_fc = w_fc.data_ptr();
+  a.b_fc = opt_ptr(b_fc);
+  a.h = h.data_ptr();
+  a.c = c.data_ptr<float>();
+  a.scratch = scratch.data_ptr<float>();
+  a.first = first.data_ptr<int64_t>();
+  a.cum = cum.data_ptr<float>();
+  a.done = done.data_ptr<int32_t>();
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.parents = parents.data_ptr<int32_t>();
+  a.lp = present(lp) ? lp->data_ptr<float>() : nullptr;
+  a.logits = present(logits) ? logits->data_ptr<float>() : nullptr;
+  a.hyp = hyp.data_ptr<int64_t>();
+  a.hyp_lp = present(hyp_lp) ? hyp_lp->data_ptr<float>() : nullptr;
+  a.G = (int)G; a.W = (int)W; a.H = (int)H; a.E = (int)E; a.V = (int)V; a.L = (int)L;
+  a.dtype = dt;
+  a.stop = (int)stop;
+  a.select_launch = select_launch ? 1 : 0;
+  HIP_LAUNCH_CHECK(pdrnn_lstm_decode_beam(&a, (int)N, cur_stream()));
+}
+
+// ONE beam selection on the caller's logits [S, V], cum [S], done [S] (bool)
+// through the last position's kernel -> (parent, token [S] int64, cum [S] fp32,
+// done [S] bool, lp [S] fp32).  out: a caller's int64 / fp32 / int32 buffers
+// (tokens [S], parents [S] int32, lp [S], cum [2, S], done [2, S] int32), for guarded runs.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lstm_decode_beam_select(
+    const Tensor& logits, const Tensor& cum, const Tensor& done, int64_t W, int64_t stop,
+    const optional<std::vector<Tensor>>& out) {
+  CHECK_HIP_TENSOR(logits);
+  const c10::DeviceGuard guard(logits.device());
+  TORCH_CHECK(logits.dim() == 2 && logits.scalar_type() == at::kFloat && logits.is_contiguous(),
+              "lstm_decode_beam_select: logits [S, V] fp32");
+  const int64_t S = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(W >= 1 && W <= 16 && S >= 1 && S <= 16 && S % W == 0 && V >= 1 && V <= 1024,
+              "lstm_decode_beam_select: 1 <= W <= 16, S = G W <= 16, V <= 1024");
+  TORCH_CHECK(stop >= -1 && stop < V, "lstm_decode_beam_select: stop in [0, V), or -1 for none");
+  TORCH_CHECK(cum.is_cuda() && cum.numel() == S && done.is_cuda() && done.numel() == S, "lstm_decode_beam_select: cum, done [S]");
+  Tensor tokens, parents, lp, cum2, done2;
+  if (out.has_value()) {
+    TORCH_CHECK(out->size() == 5, "lstm_decode_beam_select: out = (tokens, parents, lp, cum, done)");
+    tokens = (*out)[0]; parents = (*out)[1]; lp = (*out)[2]; cum2 = (*out)[3]; done2 = (*out)[4];
+    auto ok = [&](const Tensor& t, at::ScalarType ty, int64_t n) {
+      return t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.numel() == n;
+    };
+    TORCH_CHECK(ok(tokens, at::kLong, S) && ok(parents, at::kInt, S) && ok(lp, at::kFloat, S) &&
+                ok(cum2, at::kFloat, 2 * S) && ok(done2, at::kInt, 2 * S), "lstm_decode_beam_select: out buffers");
+  } else {
+    tokens = at::empty({S}, logits.options().dtype(at::kLong));
+    parents = at::empty({S}, logits.options().dtype(at::kInt));
+    lp = at::empty({S}, logits.options());
+    cum2 = at::empty({2, S}, logits.options());
+    done2 = at::empty({2, S}, logits.options().dtype(at::kInt));
+  }
+  cum2.view({2, S}).select(0, 0).copy_(cum.reshape({S}));
+  done2.view({2, S}).select(0, 0).copy_(done.reshape({S}));
+  HIP_LAUNCH_CHECK(pdrnn_lstm_decode_beam_select(logits.data_ptr<float>(), cum2.data_ptr<float>(), done2.data_ptr<int32_t>(),
+                                                 tokens.data_ptr<int64_t>(), parents.data_ptr<int32_t>(),
+                                                 lp.data_ptr<float>(), (int)(S / W), (int)W, (int)V, (int)stop,
+                                                 cur_stream()));
+  return std::make_tuple(parents.to(at::kLong), tokens, cum2.view({2, S}).select(0, 1), done2.view({2, S}).select(0, 1).ne(0),
+                         lp);
+}
+
 // Char-LM evaluation (kernels/head_nll.hip): the vocabulary head, log-softmax,
 // NLL and argmax of h [N, H] (any row stride) in one kernel; accum [3] fp64 is
 // added to.  Returns (row_nll [N] fp32, pred [N] int32), the caller's buffers when given.
@@ -2075,7 +2198,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
     return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
   }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
-  m.def("head_nll", &head_nll, "fused vocabulary head + log-softmax + NLL + argmax -> (row_nll, pred); accum += sums",
+  m.def("lstm_decode_beam", &lstm_decode_beam, "char-LM beam search: n_tokens positions of the fused decode kernels",
+        py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
+        py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("cum"), py::arg("done"),
+        py::arg("tokens"), py::arg("parents"), py::arg("lp"), py::arg("logits"), py::arg("hyp"), py::arg("hyp_lp"),
+        py::arg("G"), py::arg("W"), py::arg("stop") = -1, py::arg("select_launch") = false);
+  m.def("lstm_decode_beam_supported",
+        [](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
+          auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
+          return fits(G) && fits(W) && fits(H) && fits(E) && fits(V) && fits(L) &&
+                 pdrnn_lstm_decode_beam_supported((int)G, (int)W, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
+        }, "the decode kernels cover a beam search of G groups of W beams (dtype 0 bf16, 1 fp16, 2 fp32)");
+  m.def("lstm_decode_beam_select", &lstm_decode_beam_select,
+        "one beam selection through the last position's kernel -> (parent, token, cum, done, lp)", py::arg("logits"),
+        py::arg("cum"), py::arg("done"), py::arg("W"), py::arg("stop") = -1, py::arg("out") = py::none());
+  m.def("head_nll", &head_nll,"fused vocabulary head + log-softmax + NLL + argmax -> (row_nll, pred); accum += sums",
         py::arg("h"), py::arg("w16"), py::arg("bias"), py::arg("labels"), py::arg("ignore_index"), py::arg("accum"),
         py::arg("row_nll") = py::none(), py::arg("pred") = py::none());
   m.def("head_nll_supported", [](int64_t H, int64_t V, int64_t dtype) {

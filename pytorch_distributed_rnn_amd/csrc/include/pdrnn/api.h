@@ -518,6 +518,45 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype);
 // NaN top_p are hipErrorInvalidValue.
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
 
+// Beam search on the same kernels (pdrnn/decode_rng.h: the rule): G groups of W
+// beams, S = G W <= 16 streams, stream g W + j beam j of group g.  Selection q
+// (on position q's logits) runs inside the layer-0 launch of position q + 1,
+// the last one in a launch of its own that also traces the parents back.
+typedef struct {
+  const void* emb;           // as PdrnnLstmDecodeArgs, B = S
+  const void* const* w_ih;
+  const void* const* w_hh;
+  const float* const* bias;
+  const void* w_fc;
+  const float* b_fc;
+  void* h;                   // [2, L, S, H]: a group's W streams all start from the prompt's state
+  float* c;                  // [L, S, H], in place
+  float* scratch;            // [S, V]
+  const int64_t* first;      // [S] the prompt's last token, W times per group
+  float* cum;                // [n_tokens + 1, S]: row 0 the caller's start scores (0, -inf, ... per group),
+  int32_t* done;             // [n_tokens + 1, S]: row 0 the caller's (zeros); row q + 1 written by selection q
+  int64_t* tokens;           // [S, n_tokens] the token slot s took at selection q,
+  int32_t* parents;          // [S, n_tokens] the stream it continues,
+  float* lp;                 // [S, n_tokens] or NULL: and that token's log-prob (0 for a done beam's stop)
+  float* logits;             // [S, n_tokens, V] or NULL: per slot and position
+  int64_t* hyp;              // [S, n_tokens] the hypotheses in final rank order
+  float* hyp_lp;             // [S, n_tokens] or NULL (needs lp): the log-probs along each
+  int G, W, H, E, V, L;
+  int dtype;                 // 0 bf16, 1 fp16
+  int stop;                  // -1: none
+  int select_launch;         // 1: every selection a one-workgroup launch of its own (measurement)
+} PdrnnLstmDecodeBeamArgs;
+// the decode limits at B = G W, 1 <= W <= 16, G W <= 16
+int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype);
+// Enqueues (L + 1) * n_tokens launches and the last selection; no host read.
+// Bad arguments (a shape not supported, n_tokens < 1, stop outside [-1, V)) are hipErrorInvalidValue.
+hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream);
+// ONE selection through the last position's kernel: logits [S, V], cum / done
+// [2, S] (row 0 read, row 1 written), tokens / parents / lp [S].
+hipError_t pdrnn_lstm_decode_beam_select(const float* logits, float* cum, int32_t* done, int64_t* tokens,
+                                         int32_t* parents, float* lp, int G, int W, int V, int stop,
+                                         hipStream_t stream);
+
 // ---- char-LM evaluation (kernels/head_nll.hip) ------------------------------
 // Vocabulary head + log-softmax + NLL + argmax, the logits kept in fp32 MFMA
 // accumulators and never stored.  row_nll[r] = logsumexp(logits_r) -

@@ -1,6 +1,6 @@
 // The sampling rule of the char-LM decode path, written once: the kernels
 // (kernels/lstm_decode.hip) include it, ops/decode.py:gumbel_noise mirrors it
-// step for step.
+// step for step.  Below it the filter rule and the beam-search rule.
 //
 // Gumbel-max: token = argmax_v(logit_v / temperature + g_v), g_v = -log(-log u_v)
 // with u_v uniform in (0, 1), samples softmax(logits / temperature) with no
@@ -80,5 +80,37 @@ PDRNN_RNG_FN float decode_key_value(uint32_t k) {
   __builtin_memcpy(&x, &u, 4);
   return x;
 }
+
+// ---- beam search --------------------------------------------------------------
+// A launch holds G groups (prompts) of W beams, G W <= 16; stream s = g W + j is
+// beam j of group g (ops/decode.py:beam_select mirrors one position's rule).
+//   Start: the W streams of a group enter position 0 with the prompt's state
+//     and last token, cum[0] = 0, cum[j > 0] = -inf (the copies cannot fill the
+//     beam), done = false.
+//   Position p, from its fp32 logits l[s, :]:  m_s = max_v l[s, v],
+//     lp_s(v) = (l[s, v] - m_s) - log sum_v exp(l[s, v] - m_s)  in fp32 in that
+//     order, the max and the sum in the fixed order of the filters' wave_max /
+//     wave_sum (every workgroup gets the same bits).
+//     A live stream's candidates are every v with cand = cum_s + lp_s(v); a done
+//     stream has the single candidate v = stop with cand = cum_s, log-prob 0.
+//     Per group the W best candidates become the new beams in rank order: cand
+//     descending, then source beam j ascending, then v ascending.  -inf is an
+//     ordinary value (with V < W or at position 0 the tail fills with -inf
+//     candidates in (j, v) order); a NaN score ranks, and is kept, as -inf; -0
+//     counts as +0.
+//     New slot i: parent[i] = j, token[i] = v, cum[i] = cand,
+//     done[i] = done_j or v == stop.
+//   Next position: slot i reads the embedding row of token[i] and, in every
+//     layer, the h and c of slot parent[i].
+//   After N positions the parents are traced back into hypotheses [G, W, N] in
+//     final rank order.
+//
+// The rank of a score is the order of its key: NaN as -inf, -0 as +0.  Every
+// candidate's key is > 0, so 0 can stand for "no candidate".
+PDRNN_RNG_FN float beam_score(float cand) {
+  if (cand != cand) return -__builtin_inff();
+  return cand == 0.f ? 0.f : cand;
+}
+PDRNN_RNG_FN uint32_t beam_score_key(float cand) { return decode_order_key(beam_score(cand)); }
 
 }  // namespace pdrnn

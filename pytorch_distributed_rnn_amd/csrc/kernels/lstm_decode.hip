@@ -22,6 +22,11 @@
 //     threshold by a bitwise selection in registers (sample_tokens_filtered).
 //   * lstm_decode_head<DT>: logits = h_top W_fc^T + b_fc in fp32, 16
 //     vocabulary rows per workgroup, rows past V masked.
+//   * Beam search (the BEAM instantiations; pdrnn/decode_rng.h: the rule): G
+//     groups of W beams are G W <= 16 of the streams.  In sampling's place
+//     layer 0 selects each group's W best of its W V candidates (beam_select)
+//     and every layer reads h_{t-1} and c of stream parent[n] instead of n;
+//     the last selection and the backtrace are lstm_decode_beam_pick.
 // h ping-pongs between two buffers by token parity (every workgroup reads all
 // of h_{t-1} while the others write h_t); layer l > 0 reads layer l - 1's h_t
 // of the same token.  All ordering is kernel boundaries on one stream: nothing
@@ -265,6 +270,174 @@ __device__ __forceinline__ void sample_tokens_filtered(const SampleArgs& s, int 
   else sample_tokens_filtered_n<kSlots>(s, p, tok, thr, lp);
 }
 
+// ---- beam search (pdrnn/decode_rng.h: the rule) -------------------------------
+// What one selection reads and writes.  Selection q works on position q's
+// logits: it reads row q of cum / done and writes row q + 1 and column q of
+// tokens / parents / lp, so no workgroup reads what another writes in a launch.
+struct BeamArgs {
+  const float* scratch;  // [S, V] logits of position q, S = G W
+  float* cum;            // [N + 1, S]
+  int32_t* done;         // [N + 1, S]
+  int64_t* tokens;       // [S, N]
+  int32_t* parents;      // [S, N] stream indices of the launch
+  float* lp;             // [S, N] or null
+  int G, W, V, N;
+  int stop;              // -1: none
+  int separate;          // the selection is a launch of its own: layer 0 reads tokens / parents
+};
+
+struct BeamLds {
+  uint32_t ck[kStreams][kStreams];  // a stream's W best candidates in rank order: score keys (0: none),
+  int cv[kStreams][kStreams];       // tokens
+  float cl[kStreams][kStreams];     // and log-probs
+  int parent[kStreams], tok[kStreams], done[kStreams];  // the new slots
+  float cum[kStreams], lp[kStreams];
+};
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_peer_u(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t lane_value_u(uint32_t x, int lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)x, lane);
+}
+__device__ __forceinline__ uint32_t wave_umax(uint32_t x) {
+  x = umax(x, dpp_peer_u<0xb1>(x));
+  x = umax(x, dpp_peer_u<0x4e>(x));
+  x = umax(x, dpp_peer_u<0x141>(x));
+  x = umax(x, dpp_peer_u<0x140>(x));
+  return umax(umax(lane_value_u(x, 0), lane_value_u(x, 16)), umax(lane_value_u(x, 32), lane_value_u(x, 48)));
+}
+
+// One selection, by every lane of the workgroup; the new slots end in L.
+//   1. A wave per stream, the row in registers as in sample_tokens_filtered_n:
+//      log-softmax, score keys, then the row's W best in rank order by W rounds
+//      of (wave max of the keys, first holder by ballots: the lowest slot, then
+//      the lowest lane, is the lowest v), into LDS.  A stream contributes at
+//      most W winners, and they are among these.
+//   2. A wave per group: lane j < W holds the head of stream j's list; W rounds
+//      of (wave max of the heads, the lowest lane holding it) merge them.
+// Integer keys, ballots and fixed-order sums: the same bits in every workgroup.
+template <int NS>
+__device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds& L) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int V = b.V, W = b.W, S = b.G * b.W;
+  const float* cum = b.cum + (int64_t)q * S;
+  const int32_t* done = b.done + (int64_t)q * S;
+  for (int s = wave; s < S; s += kWaves) {
+    const float* row = b.scratch + (int64_t)s * V;
+    const float cs = cum[s];
+    const bool ds = done[s] != 0;
+    float l[NS], lpv[NS];
+    uint32_t key[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int v = lane + i * kWave;
+      l[i] = row[v < V ? v : V - 1];
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      if (lane + i * kWave >= V) l[i] = -INFINITY;
+      m = fmaxf(m, l[i]);
+    }
+    m = wave_max(m);
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      l[i] -= m;
+      acc += lane + i * kWave < V ? expf(l[i]) : 0.f;
+    }
+    const float lse = logf(wave_sum(acc));
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int v = lane + i * kWave;
+      lpv[i] = ds ? 0.f : l[i] - lse;
+      const bool cand = v < V && (!ds || v == b.stop);
+      key[i] = cand ? beam_score_key(ds ? cs : cs + lpv[i]) : 0;
+    }
+#pragma unroll 1
+    for (int r = 0; r < W; ++r) {
+      uint32_t mx = 0;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) mx = umax(mx, key[i]);
+      mx = wave_umax(mx);
+      int wv = 0;
+      float wl = 0.f;
+      if (mx != 0) {
+        bool found = false;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+          const unsigned long long bal = __builtin_amdgcn_ballot_w64(key[i] == mx);
+          if (!found && bal != 0) {
+            found = true;
+            const int at = __builtin_ctzll(bal);
+            wv = i * kWave + at;
+            wl = lane_value(lpv[i], at);
+            if (lane == at) key[i] = 0;
+          }
+        }
+      }
+      if (lane == 0) {
+        L.ck[s][r] = mx;
+        L.cv[s][r] = wv;
+        L.cl[s][r] = wl;
+      }
+    }
+  }
+  __syncthreads();
+  for (int g = wave; g < b.G; g += kWaves) {
+    const int s = g * W + (lane < W ? lane : 0);
+    int head = 0;
+#pragma unroll 1
+    for (int i = 0; i < W; ++i) {
+      const uint32_t k = lane < W && head < W ? L.ck[s][head] : 0;
+      const uint32_t mx = wave_umax(k);
+      const unsigned long long bal = __builtin_amdgcn_ballot_w64(lane < W && k == mx);
+      const int j = __builtin_ctzll(bal);  // (a group always has W candidates: lane 0 at the worst)
+      PDRNN_DEVICE_ASSERT(mx != 0);
+      if (lane == j) {
+        const int slot = g * W + i, v = head < W ? L.cv[s][head] : 0;
+        L.parent[slot] = s;
+        L.tok[slot] = v;
+        L.cum[slot] = mx != 0 ? decode_key_value(mx) : -INFINITY;
+        L.lp[slot] = head < W ? L.cl[s][head] : 0.f;
+        L.done[slot] = done[s] != 0 || v == b.stop;
+        ++head;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void beam_select(const BeamArgs& b, int q, BeamLds& L) {
+  if (b.V <= 1 * kWave) beam_select_n<1>(b, q, L);
+  else if (b.V <= 2 * kWave) beam_select_n<2>(b, q, L);
+  else if (b.V <= 4 * kWave) beam_select_n<4>(b, q, L);
+  else if (b.V <= 8 * kWave) beam_select_n<8>(b, q, L);
+  else beam_select_n<kSlots>(b, q, L);
+}
+
+// selection q's record (one workgroup's job)
+__device__ __forceinline__ void beam_record(const BeamArgs& b, int q, const BeamLds& L) {
+  const int S = b.G * b.W, s = threadIdx.x;
+  if (s >= S) return;
+  const int64_t at = (int64_t)s * b.N + q;
+  b.tokens[at] = L.tok[s];
+  b.parents[at] = L.parent[s];
+  if (b.lp != nullptr) b.lp[at] = L.lp[s];
+  b.cum[(int64_t)(q + 1) * S + s] = L.cum[s];
+  b.done[(int64_t)(q + 1) * S + s] = L.done[s];
+}
+
+// a parent held inside its group's streams: a bad value reads no memory outside the buffers
+__device__ __forceinline__ int beam_parent(int par, int n, int W) {
+  const int lo = n - n % W;
+  PDRNN_DEVICE_ASSERT(par >= lo && par < lo + W);
+  return par < lo ? lo : (par >= lo + W ? lo + W - 1 : par);
+}
+
 struct LayerArgs {
   const uint16_t* wx;     // [4H, Kx] gate-interleaved rows 4u + q
   const uint16_t* wh;     // [4H, H]
@@ -277,6 +450,7 @@ struct LayerArgs {
   const int64_t* forced;  // FIRST: [B, N] input tokens of every position, or null
   SampleArgs s;
   int H, Kx, p;
+  BeamArgs b;             // BEAM: the search (s: B, V and N only)
 };
 
 // Sum of the waves' partial accumulators, in wave order, into wave 0.
@@ -292,7 +466,17 @@ __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
 
 // FILT (layer 0 only, chosen on the host): the filtered sampler and its two
 // outputs; a launch sequence with no filter and no output wanted never runs it.
-template <class DT, bool FIRST, bool FILT = false>
+//
+// BEAM: stream n continues stream par = parent[n] of the previous position: it
+// reads h_{t-1} and c of par in every layer (x of a layer above 0 is the layer
+// below's h_t, already in new-slot order).  Layer 0 selects (beam_select; by
+// every workgroup, recorded by workgroup 0) or, with the selection a launch of
+// its own, reads that launch's record; the layers above read the record.  c
+// stays in place: a unit's 16 streams are 16 lanes of wave 0 of one workgroup,
+// which loads c[par] in one instruction and stores c[n] in a later one that
+// depends on the loaded value, so every lane's load has completed before any
+// lane's store; no other workgroup touches the unit.
+template <class DT, bool FIRST, bool FILT = false, bool BEAM = false>
 __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a) {
   __shared__ f32x4 red[kWaves][kWave];
   __shared__ int tok[kStreams];
@@ -301,9 +485,29 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   const int n = lane & 15, kq = lane >> 4;
   const int B = a.s.B, H = a.H, Kx = a.Kx;
   const bool live = n < B;
+  int par = n;  // the stream whose state stream n continues
 
   const uint16_t* xrow = a.x + (int64_t)n * Kx;  // (read only where live)
-  if constexpr (FIRST) {
+  if constexpr (BEAM && FIRST) {
+    __shared__ BeamLds L;
+    const bool select = a.p > 0 && !a.b.separate;
+    if (select) {
+      beam_select(a.b, a.p - 1, L);
+      if (blockIdx.x == 0) beam_record(a.b, a.p - 1, L);
+    }
+    int64_t t = 0;
+    if (live) {
+      if (a.p == 0) t = a.first[n];
+      else if (select) t = L.tok[n], par = L.parent[n];
+      else t = a.b.tokens[(int64_t)n * a.b.N + a.p - 1], par = a.b.parents[(int64_t)n * a.b.N + a.p - 1];
+      PDRNN_DEVICE_ASSERT(t >= 0 && t < a.s.V);
+      t = t < 0 ? 0 : (t >= a.s.V ? a.s.V - 1 : t);
+      par = beam_parent(par, n, a.b.W);
+    }
+    xrow = a.x + t * Kx;
+  } else if constexpr (BEAM) {
+    if (live && a.p > 0) par = beam_parent(a.b.parents[(int64_t)n * a.b.N + a.p - 1], n, a.b.W);
+  } else if constexpr (FIRST) {
     // the sampled token is needed as an input only when nothing is forced;
     // forced runs still record it, which is workgroup 0's job alone
     const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
@@ -338,7 +542,7 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   const uint16_t* wxr = a.wx + (int64_t)row * Kx + kq * 8;
   const uint16_t* whr = a.wh + (int64_t)row * H + kq * 8;
   const uint16_t* xr = xrow + kq * 8;
-  const uint16_t* hr = a.hprev + (int64_t)n * H + kq * 8;
+  const uint16_t* hr = a.hprev + (int64_t)par * H + kq * 8;
   const int nkx = Kx / 32, nkb = nkx + H / 32;
   const uint4 zero = make_uint4(0, 0, 0, 0);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -361,7 +565,7 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   const float gg = tanhf_fast(z[2] + bs[2]);
   const float go = sigmoidf_fast(z[3] + bs[3]);
   const int64_t at = (int64_t)n * H + u;
-  const float cn = fmaf(gf, a.c[at], gi * gg);
+  const float cn = fmaf(gf, a.c[(int64_t)par * H + u], gi * gg);
   a.c[at] = cn;
   a.hout[at] = DT::from_f(go * tanhf_fast(cn));
 }
@@ -424,6 +628,71 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_sample(const SampleArgs 
   }
 }
 
+// Selection q as a launch of its own (one workgroup): after the last position,
+// and per position when the selection is kept out of the layer-0 launch.  hyp
+// != null (the last selection): the parents are then traced back, a thread per
+// final slot, into hyp [S, N] (and hyp_lp from lp), the last column from LDS.
+__global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs b, int q, int64_t* hyp, float* hyp_lp) {
+  __shared__ BeamLds L;
+  beam_select(b, q, L);
+  beam_record(b, q, L);
+  const int S = b.G * b.W, i = threadIdx.x;
+  if (hyp == nullptr || i >= S) return;
+  int at = i;
+  for (int k = q; k >= 0; --k) {
+    const int64_t src = (int64_t)at * b.N + k, dst = (int64_t)i * b.N + k;
+    hyp[dst] = k == q ? L.tok[at] : b.tokens[src];
+    if (hyp_lp != nullptr) hyp_lp[dst] = k == q ? L.lp[at] : b.lp[src];
+    at = beam_parent(k == q ? L.parent[at] : b.parents[src], at, b.W);
+  }
+}
+
+template <class DT>
+hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
+  const int S = a->G * a->W, H = a->H, E = a->E, V = a->V, L = a->L;
+  const BeamArgs b{a->scratch, a->cum, a->done, a->tokens, a->parents, a->lp, a->G, a->W, V, n_tokens,
+                   a->stop, a->select_launch != 0};
+  SampleArgs s{};
+  s.B = S;
+  s.V = V;
+  s.N = n_tokens;
+  const uint16_t* h = static_cast<const uint16_t*>(a->h);
+  uint16_t* hm = static_cast<uint16_t*>(a->h);
+  const int64_t BH = (int64_t)S * H, slot = (int64_t)L * BH;
+  for (int p = 0; p < n_tokens; ++p) {
+    const int64_t in = (p & 1) * slot, out = ((p + 1) & 1) * slot;
+    if (b.separate && p > 0) {
+      lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(b, p - 1, nullptr, nullptr);
+      PDRNN_HIP_CHECK(hipGetLastError());
+    }
+    for (int l = 0; l < L; ++l) {
+      LayerArgs k{};
+      k.wx = static_cast<const uint16_t*>(a->w_ih[l]);
+      k.wh = static_cast<const uint16_t*>(a->w_hh[l]);
+      k.bias = a->bias[l];
+      k.x = l == 0 ? static_cast<const uint16_t*>(a->emb) : h + out + (l - 1) * BH;
+      k.hprev = h + in + l * BH;
+      k.hout = hm + out + l * BH;
+      k.c = a->c + l * BH;
+      k.first = a->first;
+      k.s = s;
+      k.H = H;
+      k.Kx = l == 0 ? E : H;
+      k.p = p;
+      k.b = b;
+      if (l == 0) lstm_decode_layer<DT, true, false, true><<<H / 4, kThreads, 0, stream>>>(k);
+      else lstm_decode_layer<DT, false, false, true><<<H / 4, kThreads, 0, stream>>>(k);
+      PDRNN_HIP_CHECK(hipGetLastError());
+    }
+    const HeadArgs hd{static_cast<const uint16_t*>(a->w_fc), a->b_fc, h + out + (L - 1) * BH, a->scratch, a->logits,
+                      S, H, V, n_tokens, p};
+    lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
+    PDRNN_HIP_CHECK(hipGetLastError());
+  }
+  lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(b, n_tokens - 1, a->hyp, a->hyp_lp);
+  return hipGetLastError();
+}
+
 template <class DT>
 hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
   const int B = a->B, H = a->H, E = a->E, V = a->V, L = a->L;
@@ -481,6 +750,31 @@ hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStre
   if (n_tokens < 1 || !pdrnn_lstm_decode_supported(a->B, a->H, a->E, a->V, a->L, a->dtype)) return hipErrorInvalidValue;
   if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
   return a->dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
+}
+
+int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype) {
+  return G >= 1 && W >= 1 && W <= pdrnn::kStreams && G <= pdrnn::kStreams && G * W <= pdrnn::kStreams &&
+         pdrnn_lstm_decode_supported(G * W, H, E, V, L, dtype);
+}
+
+hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
+  if (n_tokens < 1 || !pdrnn_lstm_decode_beam_supported(a->G, a->W, a->H, a->E, a->V, a->L, a->dtype))
+    return hipErrorInvalidValue;
+  if (a->stop < -1 || a->stop >= a->V || (a->hyp_lp != nullptr && a->lp == nullptr) || a->hyp == nullptr)
+    return hipErrorInvalidValue;
+  return a->dtype == 0 ? pdrnn::decode_beam<pdrnn::BF16>(a, n_tokens, stream)
+                       : pdrnn::decode_beam<pdrnn::F16>(a, n_tokens, stream);
+}
+
+hipError_t pdrnn_lstm_decode_beam_select(const float* logits, float* cum, int32_t* done, int64_t* tokens,
+                                         int32_t* parents, float* lp, int G, int W, int V, int stop,
+                                         hipStream_t stream) {
+  if (G < 1 || W < 1 || G > pdrnn::kStreams || W > pdrnn::kStreams || G * W > pdrnn::kStreams || V < 1 || V > 1024 ||
+      stop < -1 || stop >= V)
+    return hipErrorInvalidValue;
+  const pdrnn::BeamArgs b{logits, cum, done, tokens, parents, lp, G, W, V, 1, stop, 0};
+  pdrnn::lstm_decode_beam_pick<<<1, pdrnn::kThreads, 0, stream>>>(b, 0, nullptr, nullptr);
+  return hipGetLastError();
 }
 
 }  // extern "C"

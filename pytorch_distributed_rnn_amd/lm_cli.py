@@ -8,6 +8,8 @@
     python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-epoch0.pt \\
         --prompt "The " --num-tokens 256 --temperature 0.8 --top-k 40 --top-p 0.9 --stop-token 10 \\
         --samples 4 generate
+    python -m pytorch_distributed_rnn_amd.lm_cli --checkpoint out/charlm-epoch0.pt \\
+        --prompt "The " --num-tokens 64 --beam-width 8 --samples 3 --stop-token 10 --length-penalty 0.7 generate
 
     python -m pytorch_distributed_rnn_amd.lm_cli --text corpus.txt --validation-fraction 0.1 \\
         --checkpoint-directory out local
@@ -20,7 +22,9 @@ ends with its loss, bits per character and accuracy (``val_*`` in the
 history), and ``charlm-best.pt`` keeps the checkpoint with the lowest
 ``val_loss``.  ``generate`` and ``evaluate`` rebuild the model from the
 checkpoint alone (only ``--dtype`` is read from the command line); ``generate``
-samples ``--samples`` continuations of the prompt, ``evaluate`` scores
+samples ``--samples`` continuations of the prompt -- or, with ``--beam-width
+W``, searches for the most likely ones with W beams and prints the ``--samples``
+best (``CharLM.beam_search``; no sampling flags then) --, ``evaluate`` scores
 ``--text`` or the synthetic corpus (with ``--validation-fraction`` its held-out
 tail only: a training run's validation figure again, from its checkpoint).
 """
@@ -85,7 +89,12 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--stop-token", type=int, default=None, help="generate: a byte value; a sample ends before its first one")
     g.add_argument("--logprobs-file", default=None, help="generate: write every sample's token log-probabilities "
                                                          "(under the filtered distribution) and their sum here as JSON")
-    g.add_argument("--samples", type=int, default=1)
+    g.add_argument("--samples", type=int, default=1, help="generate: samples drawn; with --beam-width the hypotheses "
+                                                          "printed, best first (at most the width)")
+    g.add_argument("--beam-width", type=int, default=0, help="generate: beam search with this many beams (1..16) "
+                                                              "instead of sampling; 0: off")
+    g.add_argument("--length-penalty", type=float, default=0.0, help="generate, beam search: rank the final hypotheses "
+                                                                       "by score / length^A; 0: off")
     g.add_argument("--output", default=None, help="generate: write the samples' raw bytes here, one after another; "
                                                    "evaluate: write the figures here as JSON")
     p.add_argument("mode", choices=("local", "distributed", "generate", "evaluate"))
@@ -111,7 +120,10 @@ def generate(args):
     """``generate``: rebuild the model a checkpoint describes and sample
     ``--samples`` continuations of the prompt, ``--num-tokens`` tokens each.
     The samples are the rows of one batch, so they differ by their row index
-    in the sampling hash; the same ``--seed`` gives the same text again."""
+    in the sampling hash; the same ``--seed`` gives the same text again.
+    ``--beam-width W``: one beam search instead, its ``--samples`` best
+    hypotheses, best first; ``sum`` in ``--logprobs-file`` is a hypothesis's
+    score."""
     from .models.charlm import charlm_from_state_dict
     from .train import checkpoint as ckpt
     from .train.trainer import default_device
@@ -123,6 +135,13 @@ def generate(args):
         raise SystemExit("generate: --samples >= 1, --num-tokens >= 0 and --temperature >= 0")
     if args.top_k < 0 or not 0 < args.top_p <= 1:
         raise SystemExit("generate: --top-k >= 0 and --top-p in (0, 1]")
+    beam = args.beam_width != 0
+    if beam and not (1 <= args.beam_width <= 16 and args.samples <= args.beam_width and args.num_tokens >= 1):
+        raise SystemExit("generate: --beam-width in [1, 16], --samples <= --beam-width and --num-tokens >= 1")
+    if beam and (args.top_k != 0 or args.top_p != 1.0 or args.temperature != 1.0):
+        raise SystemExit("generate: --beam-width searches, it does not sample: no --top-k, --top-p or --temperature")
+    if not beam and args.length_penalty != 0:
+        raise SystemExit("generate: --length-penalty needs --beam-width")
     if args.prompt_file is not None:
         with open(args.prompt_file, "rb") as f:
             prompt = f.read()
@@ -140,17 +159,29 @@ def generate(args):
     device = torch.device(args.device) if args.device else default_device()
     model = model.to(device).eval()
     want_lp = args.logprobs_file is not None
-    out = model.generate(torch.tensor(list(prompt), dtype=torch.int64).repeat(args.samples, 1), args.num_tokens,
-                         temperature=args.temperature, seed=args.seed, top_k=args.top_k, top_p=args.top_p,
-                         stop=args.stop_token, return_logprobs=want_lp, return_lengths=True)
-    tokens, lengths = out[0].cpu().tolist(), out[-1].cpu().tolist()
-    logprobs = out[1].double().cpu() if want_lp else None
+    sums = None
+    if beam:
+        # the --samples best hypotheses of one search; a beam that found no continuation (score -inf) is left out
+        out = model.beam_search(torch.tensor([list(prompt)], dtype=torch.int64), args.num_tokens, args.beam_width,
+                                stop=args.stop_token, length_penalty=args.length_penalty, return_logprobs=want_lp)
+        keep = [i for i, s in enumerate(out[1][0].cpu().tolist()[:args.samples]) if s != float("-inf")]
+        tokens, lengths = [out[0][0].cpu().tolist()[i] for i in keep], [out[2][0].cpu().tolist()[i] for i in keep]
+        sums = [out[1][0].double().cpu().tolist()[i] for i in keep]
+        logprobs = out[3][0].double().cpu()[keep] if want_lp else None
+    else:
+        out = model.generate(torch.tensor(list(prompt), dtype=torch.int64).repeat(args.samples, 1), args.num_tokens,
+                             temperature=args.temperature, seed=args.seed, top_k=args.top_k, top_p=args.top_p,
+                             stop=args.stop_token, return_logprobs=want_lp, return_lengths=True)
+        tokens, lengths = out[0].cpu().tolist(), out[-1].cpu().tolist()
+        logprobs = out[1].double().cpu() if want_lp else None
     # a sample ends before its stop byte; its log-probs include the stop's
     samples = [bytes(row[:n - 1] if n and row[n - 1] == args.stop_token else row[:n]) for row, n in zip(tokens, lengths)]
     if want_lp:
+        if sums is None:
+            sums = [float(lp[:n].sum()) for lp, n in zip(logprobs, lengths)]
         with open(args.logprobs_file, "w") as f:
-            json.dump({"samples": [{"length": n, "logprobs": lp[:n].tolist(), "sum": float(lp[:n].sum())}
-                                   for lp, n in zip(logprobs, lengths)]}, f)
+            json.dump({"samples": [{"length": n, "logprobs": lp[:n].tolist(), "sum": s}
+                                   for lp, n, s in zip(logprobs, lengths, sums)]}, f)
     if args.output:
         with open(args.output, "wb") as f:
             f.write(b"".join(samples))

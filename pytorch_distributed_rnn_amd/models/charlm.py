@@ -174,6 +174,81 @@ class CharLM(nn.Module):
                + ((lengths,) if return_lengths else ()) + ((state,) if return_state else ()))
         return out[0] if len(out) == 1 else out
 
+    @torch.no_grad()
+    def beam_search(self, prompt: Tensor, num_tokens: int, beam_width: int, stop: Optional[int] = None,
+                    length_penalty: float = 0.0, state: Optional[Tuple[Tensor, Tensor]] = None,
+                    return_logprobs: bool = False, return_state: bool = False):
+        """The ``beam_width`` most likely continuations of ``prompt`` [B, P]
+        (P >= 1) found by beam search -> tokens [B, W, num_tokens] int64 best
+        first, scores [B, W] fp32, lengths [B, W] int64 (, per-token log-probs
+        [B, W, num_tokens] fp32 along each hypothesis) (, (h, c) [layers,
+        B * W, H], row b * W + i hypothesis i's).
+
+        The rule is ops/decode.py's: a hypothesis's score is the sum of its
+        tokens' log-probs (softmax of the fp32 logits); ties keep the lower
+        source beam, then the lower token; a prompt's unused beams (fewer than
+        W continuations exist, or survive) score -inf.  With ``stop`` a
+        hypothesis ends at its first ``stop`` token: its score freezes, its
+        later tokens are ``stop`` with log-prob 0 and its length counts up to
+        and including that ``stop``; the state is the full run's, as in
+        ``generate``.  ``length_penalty`` a != 0 re-ranks the final W by score /
+        length^a, and that quotient is the score returned.  Deterministic:
+        no seed.
+
+        Routing as in ``generate``: ``prompt[:, :-1]`` runs through ``forward``
+        from ``state``; 16-bit models the decode kernels cover run on them,
+        ``16 // beam_width`` prompts per call; everything else takes the
+        reference path, ``forward`` one token at a time -- an error under
+        ``PDRNN_KERNELS=hip-strict``.  Dropout is off and the truncated-BPTT
+        carry is left as it was."""
+        from .. import _ext
+        from ..ops import decode as dec
+        if prompt.dim() != 2 or prompt.shape[1] < 1:
+            raise ValueError("beam_search: prompt must be [B, P] with P >= 1")
+        V, E, H, L = self.vocab_size, self.embedding.embedding_dim, self.hidden_dim, self.num_layers
+        dec.check_beam(beam_width, stop, V, num_tokens)
+        dev = self.embedding.weight.device
+        prompt = prompt.to(dev, torch.int64)
+        if prompt.device.type == "cpu" and prompt.numel() and not (0 <= int(prompt.min()) and int(prompt.max()) < V):
+            raise ValueError("beam_search: prompt holds tokens outside the vocabulary")
+        B, P = prompt.shape
+        N, W = int(num_tokens), int(beam_width)
+        kept, training = self._state, self.training
+        self.eval()
+        try:
+            if P > 1:
+                _, state = self._step(prompt[:, :-1], state)
+            first = prompt[:, -1]
+            cdt = self._cdt(dev)
+            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+            per = dec.MAX_STREAMS // W
+            if plain and dec.beam_supported(min(B, per), W, H, E, V, L, cdt, dev):
+                outs = []
+                for b0 in range(0, B, per):
+                    rows = slice(b0, min(b0 + per, B))
+                    outs.append(dec.beam_decode(
+                        self.embedding.weight, self.lstm._weights(), self.fc.weight, self.fc.bias, cdt,
+                        state[0][:, rows] if state is not None else None, state[1][:, rows] if state is not None else None,
+                        first[rows], N, W, stop=stop, return_logprobs=return_logprobs))
+            else:
+                _ext.fallback(f"char-LM beam search (B={B}, W={W}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
+                o = dec.beam_reference(self._step, state, first, N, W, stop=stop, return_logprobs=return_logprobs)
+                outs = [o[:3] + tuple(o[3])]
+            hyp, scores = torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0).float()
+            logprobs = torch.cat([o[2] for o in outs], 0).float() if return_logprobs else None
+            h, c = torch.cat([o[3] for o in outs], 1), torch.cat([o[4] for o in outs], 1)
+        finally:
+            self._state = kept
+            self.train(training)
+        order, lengths, scores = dec.beam_finish(hyp, scores, stop, length_penalty)
+        if length_penalty:
+            hyp = hyp.gather(1, order[:, :, None].expand_as(hyp))
+            if logprobs is not None:
+                logprobs = logprobs.gather(1, order[:, :, None].expand_as(logprobs))
+            rows = (order + torch.arange(B, device=dev)[:, None] * W).reshape(-1)
+            h, c = h.index_select(1, rows), c.index_select(1, rows)
+        return ((hyp, scores, lengths) + ((logprobs,) if return_logprobs else ())
+                + (((h, c),) if return_state else ()))
 
     @torch.no_grad()
     def score(self, inputs: Tensor, targets: Tensor, state: Optional[Tuple[Tensor, Tensor]] = None,

@@ -34,6 +34,31 @@ same argmax over ``{v : logit_v >= tau}`` with the same noise:
 The log-probability of a drawn token is that under the kept, renormalised
 distribution: ``logit_tok / T - max - log(sum{w_v : kept})``.  Greedy ignores
 both filters, and its log-probability is the argmax's at temperature 1.
+
+Beam search (``beam_select`` is the mirror of one position; ``beam_decode`` the
+fused op, ``beam_reference`` the host loop; decode_rng.h states the rule once).
+A launch holds G groups (prompts) of W beams, G * W <= 16; stream ``s = g * W +
+j`` is beam j of group g.
+
+    start   the W streams of a group enter position 0 with the prompt's state
+            and last token; cum[0] = 0, cum[j > 0] = -inf, done = false
+    score   from the position's fp32 logits: m = max_v l[s, v], lp_s(v) =
+            (l[s, v] - m) - log(sum_v exp(l[s, v] - m)) in fp32 in that order;
+            a live stream's candidates are every v at cum_s + lp_s(v), a done
+            stream's only one is v = stop at cum_s with log-prob 0
+    select  per group the W best candidates become the new beams in rank
+            order: score descending, then source beam j, then v, ascending;
+            -inf is an ordinary value, a NaN score ranks (and is kept) as -inf
+    slot i  parent[i] = j, token[i] = v, cum[i] = the score, done[i] = done_j
+            or v == stop; at the next position it reads token[i]'s embedding
+            row and, in every layer, the h and c of slot parent[i]
+    end     after N positions the parents are traced back into hypotheses
+            [G, W, N] in final rank order; a length counts up to and including
+            the first stop, later tokens are stop with log-prob 0; finished
+            beams keep running through the LSTM on stop tokens
+
+``length_penalty`` a re-ranks the final W, stably, by cum / length^a
+(``beam_finish``): at the end only, on the device.
 """
 from __future__ import annotations
 
@@ -47,9 +72,13 @@ from . import shadow as _sh
 from .lstm_large import _DTYPE_CODE, _bias_cat, shadow
 
 __all__ = ["gumbel_noise", "keep_threshold", "token_logprobs", "check_filters", "sample", "supported", "alloc_buffers",
-           "decode", "reference", "MAX_STREAMS"]
+           "decode", "reference", "MAX_STREAMS", "check_beam", "beam_start", "beam_select", "beam_backtrace", "beam_finish",
+           "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
 
 MAX_STREAMS = 16  # streams per launch: the 16-wide side of the MFMA tile
+# beam search: every selection a one-workgroup launch of its own instead of inside the layer-0 launch.
+# The same results; slower where measured (profiles/r15/beam.md), kept for that measurement.
+BEAM_SELECT_LAUNCH = False
 _M32 = 0xFFFFFFFF
 
 
@@ -247,6 +276,217 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
                         logprobs=bufs["logprobs"] if return_logprobs else None)
     out = (bufs["tokens"], bufs["logits"] if return_logits else None, h[N & 1], c)
     return out + ((bufs["threshold"],) if return_threshold else ()) + ((bufs["logprobs"],) if return_logprobs else ())
+
+
+def check_beam(width: int, stop: Optional[int], V: int, num_tokens: int = 1, groups: int = 1) -> None:
+    """ValueError unless 1 <= width <= 16, groups * width <= 16, stop is None
+    or a token of the vocabulary, and num_tokens >= 1."""
+    if int(width) != width or not 1 <= width <= MAX_STREAMS:
+        raise ValueError(f"beam_width must be an integer in [1, {MAX_STREAMS}], not {width}")
+    if groups < 1 or groups * width > MAX_STREAMS:
+        raise ValueError(f"{groups} groups of {width} beams do not fit a launch's {MAX_STREAMS} streams")
+    if stop is not None and not 0 <= int(stop) < V:
+        raise ValueError(f"stop token {stop} is outside the vocabulary")
+    if int(num_tokens) < 1:
+        raise ValueError("num_tokens must be at least 1")
+
+
+def beam_start(groups: int, width: int, device=None, dtype: torch.dtype = torch.float32) -> Tensor:
+    """The scores [groups * width] entering position 0: 0 for a group's beam
+    0, -inf for its copies."""
+    cum = torch.full((groups, width), float("-inf"), device=device, dtype=dtype)
+    cum[:, 0] = 0
+    return cum.reshape(-1)
+
+
+def beam_select(logits: Tensor, cum: Tensor, done: Tensor, width: int, stop: Optional[int] = None):
+    """One position of the beam rule for logits [S, V] (fp32: the reference
+    path's; fp64: a test's yardstick), scores ``cum`` [S] and ``done`` [S]
+    (bool), S = G * width streams, on their device -> (parent [S] int64 stream
+    indices, token [S] int64, cum [S], done [S] bool, lp [S]) of the new slots.
+    A done stream needs ``stop``: that token is its only candidate."""
+    S, V = logits.shape
+    W = int(width)
+    G = S // W
+    if G * W != S:
+        raise ValueError(f"beam_select: {S} streams are no multiple of the width {W}")
+    dt, dev = logits.dtype, logits.device
+    cum, done = cum.to(dev, dt).reshape(S, 1), done.to(dev).to(torch.bool).reshape(S, 1)
+    ninf = torch.full((), float("-inf"), dtype=dt, device=dev)
+    d = logits - logits.max(dim=-1, keepdim=True).values
+    lp = d - torch.log(torch.exp(d).sum(dim=-1, keepdim=True))
+    lp = torch.where(done, torch.zeros_like(lp), lp)
+    cand = cum + lp
+    cand = torch.where(torch.isnan(cand), ninf, cand) + 0.0  # (NaN ranks as -inf; -0 + 0 = +0)
+    v = torch.arange(V, device=dev)
+    absent = done & (v != (-1 if stop is None else int(stop)))[None, :]
+    flat, gone = cand.reshape(G, W * V), absent.reshape(G, W * V)
+    # (j, v) ascending is the flat order: a stable sort keeps it among equal scores
+    by_score = flat.sort(dim=-1, descending=True, stable=True).indices
+    present_first = gone.gather(-1, by_score).to(torch.int8).sort(dim=-1, stable=True).indices
+    idx = by_score.gather(-1, present_first)[:, :W]
+    parent = (idx // V + torch.arange(G, device=dev)[:, None] * W).reshape(S)
+    token = (idx % V).reshape(S)
+    new_done = done.reshape(S)[parent] | (token == (-1 if stop is None else int(stop)))
+    return parent, token, flat.gather(-1, idx).reshape(S), new_done, lp.reshape(G, W * V).gather(-1, idx).reshape(S)
+
+
+def beam_backtrace(tokens: Tensor, parents: Tensor, lp: Optional[Tensor] = None):
+    """Hypotheses [S, N] in final slot order from the per-selection records
+    tokens / parents (/ lp) [S, N] -> (hyp, hyp_lp or None)."""
+    S, N = tokens.shape
+    at = torch.arange(S, device=tokens.device)
+    hyp = torch.empty_like(tokens)
+    hyp_lp = torch.empty_like(lp) if lp is not None else None
+    for q in range(N - 1, -1, -1):
+        hyp[:, q] = tokens[at, q]
+        if lp is not None:
+            hyp_lp[:, q] = lp[at, q]
+        at = parents[at, q].to(torch.int64)
+    return hyp, hyp_lp
+
+
+def beam_finish(hyp: Tensor, scores: Tensor, stop: Optional[int], length_penalty: float = 0.0):
+    """Lengths and the final order, on the device with no host read: hyp
+    [G, W, N], scores [G, W] in rank order -> (order [G, W], lengths [G, W]
+    int64, ranked scores [G, W]).  A length counts up to and including the first
+    ``stop``; ``length_penalty`` a != 0 re-ranks, stably, by score / length^a."""
+    hit = hyp == stop if stop is not None else torch.zeros_like(hyp, dtype=torch.bool)
+    before = hit.cumsum(dim=-1) - hit.to(torch.int64)
+    lengths = (before == 0).sum(dim=-1).to(torch.int64)
+    order = torch.arange(hyp.shape[1], device=hyp.device).expand(hyp.shape[0], -1)
+    if length_penalty:
+        scores = scores / lengths.to(scores.dtype) ** float(length_penalty)
+        order = torch.where(torch.isnan(scores), torch.full_like(scores, float("-inf")), scores).sort(
+            dim=-1, descending=True, stable=True).indices
+        scores, lengths = scores.gather(-1, order), lengths.gather(-1, order)
+    return order, lengths, scores
+
+
+def beam_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
+    """The fused decode kernels run a beam search of G groups of W beams."""
+    device = torch.device(device)
+    if device.type != "cuda" or dtype not in _DTYPE_CODE:
+        return False
+    mod = _ext.native(device)
+    if mod is None:
+        return False
+    if not hasattr(mod, "lstm_decode_beam"):
+        raise RuntimeError("the native extension has no lstm_decode_beam: rebuild it (python -m pytorch_distributed_rnn_amd._build)")
+    return bool(mod.lstm_decode_beam_supported(G, W, H, E, V, L, _DTYPE_CODE[dtype]))
+
+
+def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torch.dtype, device,
+                       return_logits: bool = False, return_logprobs: bool = False) -> Dict[str, Optional[Tensor]]:
+    """The buffers one ``beam_decode`` call works in, S = G * W: ``h``
+    [2, L, S, H], ``c`` [L, S, H], ``scratch`` [S, V] as in ``alloc_buffers``;
+    ``cum`` [N + 1, S] fp32 and ``done`` [N + 1, S] int32 (row q enters
+    position q); ``tokens`` [S, N] int64, ``parents`` [S, N] int32 and ``lp``
+    [S, N] fp32 or None per selection; ``logits`` [S, N, V] or None per slot and
+    position; ``hyp`` [S, N] int64 and ``hyp_lp`` [S, N] or None: the traced-back
+    hypotheses."""
+    S = G * W
+    f32 = dict(device=device, dtype=torch.float32)
+    i64 = dict(device=device, dtype=torch.int64)
+    i32 = dict(device=device, dtype=torch.int32)
+    return {"h": torch.empty(2, L, S, H, device=device, dtype=cdt), "c": torch.empty(L, S, H, **f32),
+            "scratch": torch.empty(S, V, **f32), "cum": torch.empty(N + 1, S, **f32), "done": torch.empty(N + 1, S, **i32),
+            "tokens": torch.empty(S, N, **i64), "parents": torch.empty(S, N, **i32),
+            "lp": torch.empty(S, N, **f32) if return_logprobs else None,
+            "logits": torch.empty(S, N, V, **f32) if return_logits else None, "hyp": torch.empty(S, N, **i64),
+            "hyp_lp": torch.empty(S, N, **f32) if return_logprobs else None}
+
+
+def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt: torch.dtype,
+                h0: Optional[Tensor], c0: Optional[Tensor], first: Tensor, num_tokens: int, width: int, *,
+                stop: Optional[int] = None, return_logits: bool = False, return_logprobs: bool = False,
+                bufs: Optional[Dict[str, Optional[Tensor]]] = None, select_launch: Optional[bool] = None):
+    """Beam search over ``num_tokens`` positions on the fused kernels: G =
+    len(first) prompts, ``width`` beams each, G * width <= 16.
+
+    The weights as in ``decode`` (16-bit copies from the shadow registry); h0 /
+    c0 [L, G, H] or None: each prompt's state, which all its beams start from;
+    first [G]: the prompts' last tokens.  ``bufs``: caller-made buffers
+    (``alloc_beam_buffers``); they keep every selection's record.
+    ``select_launch``: every selection in a launch of its own instead of inside
+    the layer-0 launch (the measured alternative; the same results; None:
+    ``BEAM_SELECT_LAUNCH``).  Returns
+    (hyp [G, W, N] int64 in rank order, scores [G, W] fp32, hyp_lp [G, W, N] or
+    None, h [L, G * W, H] in ``cdt``, c [L, G * W, H] fp32): the state entering
+    position N of each hypothesis, the last token not fed, as in ``decode``."""
+    dev = emb_w.device
+    mod = _ext.native(dev)
+    V, E = emb_w.shape
+    H = fc_w.shape[1]
+    L = len(lstm_weights) // 4
+    G, N, W = first.shape[0], int(num_tokens), int(width)
+    check_beam(width, stop, V, N, G)
+    if mod is None or not beam_supported(G, W, H, E, V, L, cdt, dev):
+        raise RuntimeError(f"lstm_decode_beam does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
+    S = G * W
+    with torch.no_grad():
+        w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
+        w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
+        bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, dev) for l in range(L)]
+        emb16, fc16 = _sh.cast(emb_w, cdt), _sh.cast(fc_w, cdt)
+        if bufs is None:
+            bufs = alloc_beam_buffers(L, G, W, H, V, N, cdt, dev, return_logits, return_logprobs)
+        h, c = bufs["h"], bufs["c"]
+        h[0].view(L, G, W, H).copy_(h0[:, :, None, :]) if h0 is not None else h[0].zero_()
+        c.view(L, G, W, H).copy_(c0[:, :, None, :]) if c0 is not None else c.zero_()
+        bufs["cum"][0].copy_(beam_start(G, W, dev))
+        bufs["done"][0].zero_()
+        mod.lstm_decode_beam(emb16, w_ih, w_hh, bias, fc16, fc_b.detach().float() if fc_b is not None else None, h, c,
+                             bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(), bufs["cum"],
+                             bufs["done"], bufs["tokens"], bufs["parents"], bufs["lp"] if return_logprobs else None,
+                             bufs["logits"] if return_logits else None, bufs["hyp"],
+                             bufs["hyp_lp"] if return_logprobs else None, G, W, -1 if stop is None else int(stop),
+                             BEAM_SELECT_LAUNCH if select_launch is None else bool(select_launch))
+        last = bufs["parents"][:, N - 1].to(torch.int64)
+        hn, cn = h[N & 1].index_select(1, last), c.index_select(1, last)
+    return (bufs["hyp"].view(G, W, N), bufs["cum"][N].view(G, W),
+            bufs["hyp_lp"].view(G, W, N) if return_logprobs else None, hn, cn)
+
+
+def beam_reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], state, first: Tensor, num_tokens: int,
+                   width: int, *, stop: Optional[int] = None, return_logprobs: bool = False,
+                   return_trace: bool = False, dtype: torch.dtype = torch.float32):
+    """The same search as a host loop: ``step(tokens [S, 1], state) -> (logits
+    [S, V], state)`` once per position on S = G * width streams, ``state`` a
+    tuple of [layers, streams, H] tensors (or None), then ``beam_select`` in
+    ``dtype`` and a gather of the state by the parents.  Returns (hyp
+    [G, W, N], scores [G, W], hyp_lp [G, W, N] or None, state) as
+    ``beam_decode`` does, then, asked for, the trace: a dict of ``tokens``,
+    ``parents``, ``lp`` [S, N], ``cum``, ``done`` [N + 1, S] and ``logits``
+    [S, N, V]."""
+    G, N, W = first.shape[0], int(num_tokens), int(width)
+    dev = first.device
+    S = G * W
+    src = torch.arange(G, device=dev).repeat_interleave(W)
+    with torch.no_grad():
+        if state is not None:
+            state = tuple(x.index_select(1, src) for x in state)
+        tok = first[src]
+        cum, done = beam_start(G, W, dev, dtype), torch.zeros(S, dtype=torch.bool, device=dev)
+        toks, pars, lps, cums, dones, lgs = [], [], [], [cum], [done], []
+        parent = torch.arange(S, device=dev)
+        for p in range(N):
+            logits, state = step(tok.reshape(S, 1), state)
+            logits = logits.to(dtype)
+            parent, tok, cum, done, lp = beam_select(logits, cum, done, W, stop)
+            toks.append(tok), pars.append(parent), lps.append(lp), cums.append(cum), dones.append(done)
+            if return_trace:
+                lgs.append(logits)
+            if p + 1 < N:
+                state = tuple(x.index_select(1, parent) for x in state)
+        state = tuple(x.index_select(1, parent) for x in state)
+        tokens, parents, lp = torch.stack(toks, 1), torch.stack(pars, 1), torch.stack(lps, 1)
+        hyp, hyp_lp = beam_backtrace(tokens, parents, lp if return_logprobs else None)
+    out = (hyp.view(G, W, N), cum.view(G, W), hyp_lp.view(G, W, N) if return_logprobs else None, state)
+    if return_trace:
+        out += ({"tokens": tokens, "parents": parents, "lp": lp, "cum": torch.stack(cums), "done": torch.stack(dones),
+                 "logits": torch.stack(lgs, 1)},)
+    return out
 
 
 def reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], state, first: Tensor, num_tokens: int, *,
