@@ -106,7 +106,8 @@ def measure_peak_rss(fn: Callable[[], Any], interval: float = 0.01) -> Tuple[flo
 
 
 def device_peak_mib(device=None) -> float:
-    if torch.cuda.is_available():
+    # (a CPU run on a machine with a GPU has no device peak: torch rejects the query)
+    if torch.cuda.is_available() and (device is None or torch.device(device).type == "cuda"):
         return torch.cuda.max_memory_allocated(device) / 2 ** 20
     return 0.0
 
