@@ -22,9 +22,9 @@ filters (and return the tokens' log-probabilities); the defaults are off, which
 is the plain sampler the figures of profiles/r11 were taken with.
 
 ``--beam-width W ...``: beam search instead (``CharLM.beam_search``, one
-prompt): per width, the reference path, the fused path, the fused path with
-every selection a launch of its own, and plain fused sampling of W streams
-alternate in one process after the warm-up; one JSON line per width.
+prompt): per width, the reference path, the fused path and plain fused
+sampling of W streams alternate in one process after the warm-up; one JSON
+line per width.
 
     python bench/decode_bench.py [--pairs 5] [--warmup 2] [--tokens 512] [--batches 1 4 16] [--out FILE]
                                  [--top-k 40] [--top-p 0.9] [--logprobs] [--beam-width 1 4 16]
@@ -46,26 +46,24 @@ import torch  # noqa: E402
 
 
 def beam(args, model, dec, dev, cdt, generate) -> int:
-    """``--beam-width``: per width W one JSON line.  After a warm-up, four
+    """``--beam-width``: per width W one JSON line.  After a warm-up, three
     calls alternate ``--pairs`` times in one process: ``CharLM.beam_search`` on
     the reference path (``beam_reference`` over ``forward``, reached by making
-    ``ops.decode.beam_supported`` answer no), on the fused kernels with the
-    selection inside the layer-0 launch, on the fused kernels with every
-    selection a launch of its own, and plain fused sampling of W streams.
-    Microseconds per position of one prompt's search."""
+    ``ops.decode.beam_supported`` answer no), on the fused kernels, and plain
+    fused sampling of W streams.  Microseconds per position of one prompt's
+    search."""
     import warnings
     real = dec.beam_supported
     prompt = torch.zeros(1, 1, dtype=torch.int64, device=dev)
 
-    def search(W, fused: bool, select_launch: bool = False):
+    def search(W, fused: bool):
         dec.beam_supported = real if fused else (lambda *a, **k: False)
-        dec.BEAM_SELECT_LAUNCH = select_launch
         try:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
                 return model.beam_search(prompt, args.tokens, W)[0].cpu()
         finally:
-            dec.beam_supported, dec.BEAM_SELECT_LAUNCH = real, False
+            dec.beam_supported = real
 
     def timed(fn) -> float:
         torch.cuda.synchronize()
@@ -82,7 +80,7 @@ def beam(args, model, dec, dev, cdt, generate) -> int:
         assert real(1, W, args.hidden, args.embed, args.vocab, args.layers, cdt, dev), f"the decode kernels do not cover W = {W}"
         streams = torch.zeros(W, 1, dtype=torch.int64, device=dev)
         calls = {"reference": lambda: search(W, False), "fused": lambda: search(W, True),
-                 "fused_select_launch": lambda: search(W, True, True), "sampling": lambda: generate(streams, True)}
+                 "sampling": lambda: generate(streams, True)}
         for _ in range(args.warmup):
             outs = {k: f() for k, f in calls.items()}
         rounds = [{k: timed(f) for k, f in calls.items()} for _ in range(args.pairs)]
@@ -93,8 +91,6 @@ def beam(args, model, dec, dev, cdt, generate) -> int:
             rec[k + "_us_per_token"] = summary([r[k] for r in rounds])
         rec["speedup_of_medians"] = round(rec["reference_us_per_token"]["median"] / rec["fused_us_per_token"]["median"], 2)
         rec["fused_wins_every_round"] = all(r["fused"] < r["reference"] for r in rounds)
-        rec["in_launch_wins_every_round"] = all(r["fused"] < r["fused_select_launch"] for r in rounds)
-        rec["placements_agree"] = bool((outs["fused"] == outs["fused_select_launch"]).all())
         # (not a pass criterion: how long the two paths' best hypotheses agree)
         rec["best_equal_prefix"] = int((outs["fused"][0, 0] == outs["reference"][0, 0]).long().cumprod(0).sum())
         lines.append(json.dumps(rec))

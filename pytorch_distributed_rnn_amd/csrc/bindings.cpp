@@ -1787,6 +1787,77 @@ Tensor gemm_nt(const Tensor& A, const Tensor& Bt, int64_t tile) {
   return C;
 }
 
+// What the decode bindings ask of a buffer: on the device, contiguous, of the type.
+bool dev_of(const Tensor& t, at::ScalarType ty) { return t.is_cuda() && t.scalar_type() == ty && t.is_contiguous(); }
+bool dev_f32(const Tensor& t) { return dev_of(t, at::kFloat); }
+bool dev_i64(const Tensor& t) { return dev_of(t, at::kLong); }
+bool dev_i32(const Tensor& t) { return dev_of(t, at::kInt); }
+bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+float* opt_mut(const optional<Tensor>& t) { return present(t) ? t->data_ptr<float>() : nullptr; }
+
+// The filled stack and the per-layer pointer arrays it points into.
+struct DecodeStack {
+  PdrnnLstmDecodeStack stack{};
+  std::vector<const void*> w_ih, w_hh;
+  std::vector<const float*> bias;
+  DecodeStack() = default;
+  DecodeStack(DecodeStack&&) = default;  // (a move keeps the arrays where they are; a copy would not)
+  DecodeStack(const DecodeStack&) = delete;
+};
+
+// The checks lstm_decode and lstm_decode_beam share, `what` the message prefix:
+// the stack's weights and the working buffers of B = h.size(2) streams and N positions.
+// They run before the search's own G / W checks, so a search with too many
+// streams is refused here as "unsupported shape B=..." (B: its S = G W).
+DecodeStack check_decode_stack(const char* what, const Tensor& emb, const std::vector<Tensor>& w_ih,
+                               const std::vector<Tensor>& w_hh, const std::vector<Tensor>& bias, const Tensor& w_fc,
+                               const optional<Tensor>& b_fc, const Tensor& h, const Tensor& c, const Tensor& scratch,
+                               const Tensor& first, const optional<Tensor>& logits, int64_t N) {
+  const int dt = dtype_code(emb);
+  const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
+  TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
+              what, ": emb [V, E], one w_ih / w_hh / bias per layer");
+  TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
+              what, ": h [2, L, B, H] in the weights' dtype");
+  const int64_t B = h.size(2), H = h.size(3);
+  TORCH_CHECK(pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
+              what, ": unsupported shape B=", B, " H=", H, " E=", E, " V=", V, " L=", L, " N=", N);
+  DecodeStack d;
+  auto weight = [&](const Tensor& w, int64_t rows, int64_t cols) {
+    return w.is_cuda() && w.is_contiguous() && dtype_code(w) == dt && w.dim() == 2 && w.size(0) == rows &&
+           w.size(1) == cols && aligned16(w);
+  };
+  for (int64_t l = 0; l < L; ++l) {
+    TORCH_CHECK(weight(w_ih[l], 4 * H, l == 0 ? E : H), what, ": w_ih [4H, I]");
+    TORCH_CHECK(weight(w_hh[l], 4 * H, H), what, ": w_hh [4H, H]");
+    TORCH_CHECK(dev_f32(bias[l]) && bias[l].numel() == 4 * H, what, ": bias [4H] fp32");
+    d.w_ih.push_back(w_ih[l].data_ptr());
+    d.w_hh.push_back(w_hh[l].data_ptr());
+    d.bias.push_back(bias[l].data_ptr<float>());
+  }
+  TORCH_CHECK(weight(w_fc, V, H) && aligned16(emb) && aligned16(h), what, ": w_fc [V, H]");
+  if (present(b_fc)) TORCH_CHECK(dev_f32(*b_fc) && b_fc->numel() == V, what, ": b_fc [V] fp32");
+  TORCH_CHECK(dev_f32(c) && c.numel() == L * B * H, what, ": c [L, B, H] fp32");
+  TORCH_CHECK(dev_f32(scratch) && scratch.numel() == B * V, what, ": scratch [B, V] fp32");
+  TORCH_CHECK(dev_i64(first) && first.numel() == B, what, ": first [B] int64");
+  if (present(logits)) TORCH_CHECK(dev_f32(*logits) && logits->numel() == B * N * V, what, ": logits [B, N, V] fp32");
+  PdrnnLstmDecodeStack& s = d.stack;
+  s.emb = emb.data_ptr();
+  s.w_ih = d.w_ih.data();
+  s.w_hh = d.w_hh.data();
+  s.bias = d.bias.data();
+  s.w_fc = w_fc.data_ptr();
+  s.b_fc = opt_ptr(b_fc);
+  s.h = h.data_ptr();
+  s.c = c.data_ptr<float>();
+  s.scratch = scratch.data_ptr<float>();
+  s.first = first.data_ptr<int64_t>();
+  s.logits = opt_mut(logits);
+  s.B = (int)B; s.H = (int)H; s.E = (int)E; s.V = (int)V; s.L = (int)L;
+  s.dtype = dt;
+  return d;
+}
+
 // Char-LM generation (kernels/lstm_decode.hip): n_tokens positions of the
 // decode kernels, enqueued here in one go.  The buffers are the caller's (ops/decode.py).
 void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
@@ -1797,71 +1868,30 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
                  const optional<Tensor>& logprobs) {
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
-  const int dt = dtype_code(emb);
-  const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
-  TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
-              "lstm_decode: emb [V, E], one w_ih / w_hh / bias per layer");
-  TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
-              "lstm_decode: h [2, L, B, H] in the weights' dtype");
-  const int64_t B = h.size(2), H = h.size(3), N = tokens.dim() == 2 ? tokens.size(1) : 0;
-  TORCH_CHECK(pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
-              "lstm_decode: unsupported shape B=", B, " H=", H, " E=", E, " V=", V, " L=", L, " N=", N);
-  auto aligned = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
-  auto f32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
-  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
-  std::vector<const void*> pi(L), ph(L);
-  std::vector<const float*> pb(L);
-  for (int64_t l = 0; l < L; ++l) {
-    const int64_t I = l == 0 ? E : H;
-    TORCH_CHECK(w_ih[l].is_cuda() && w_ih[l].is_contiguous() && dtype_code(w_ih[l]) == dt && w_ih[l].dim() == 2 &&
-                w_ih[l].size(0) == 4 * H && w_ih[l].size(1) == I && aligned(w_ih[l]), "lstm_decode: w_ih [4H, I]");
-    TORCH_CHECK(w_hh[l].is_cuda() && w_hh[l].is_contiguous() && dtype_code(w_hh[l]) == dt && w_hh[l].dim() == 2 &&
-                w_hh[l].size(0) == 4 * H && w_hh[l].size(1) == H && aligned(w_hh[l]), "lstm_decode: w_hh [4H, H]");
-    TORCH_CHECK(f32(bias[l]) && bias[l].numel() == 4 * H, "lstm_decode: bias [4H] fp32");
-    pi[l] = w_ih[l].data_ptr();
-    ph[l] = w_hh[l].data_ptr();
-    pb[l] = bias[l].data_ptr<float>();
-  }
-  TORCH_CHECK(w_fc.is_cuda() && w_fc.is_contiguous() && dtype_code(w_fc) == dt && w_fc.dim() == 2 && w_fc.size(0) == V &&
-              w_fc.size(1) == H && aligned(w_fc) && aligned(emb) && aligned(h), "lstm_decode: w_fc [V, H]");
-  if (present(b_fc)) TORCH_CHECK(f32(*b_fc) && b_fc->numel() == V, "lstm_decode: b_fc [V] fp32");
-  TORCH_CHECK(f32(c) && c.numel() == L * B * H, "lstm_decode: c [L, B, H] fp32");
-  TORCH_CHECK(f32(scratch) && scratch.numel() == B * V, "lstm_decode: scratch [B, V] fp32");
-  TORCH_CHECK(i64(first) && first.numel() == B, "lstm_decode: first [B] int64");
-  TORCH_CHECK(i64(tokens) && tokens.size(0) == B, "lstm_decode: tokens [B, N] int64");
-  if (present(forced)) TORCH_CHECK(i64(*forced) && forced->dim() == 2 && forced->size(0) == B && forced->size(1) == N,
+  const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
+  const DecodeStack d = check_decode_stack("lstm_decode", emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+  const int64_t B = d.stack.B;
+  TORCH_CHECK(dev_i64(tokens) && tokens.size(0) == B, "lstm_decode: tokens [B, N] int64");
+  if (present(forced)) TORCH_CHECK(dev_i64(*forced) && forced->dim() == 2 && forced->size(0) == B && forced->size(1) == N,
                                    "lstm_decode: forced [B, N] int64");
-  if (present(logits)) TORCH_CHECK(f32(*logits) && logits->numel() == B * N * V, "lstm_decode: logits [B, N, V] fp32");
   TORCH_CHECK(temperature >= 0.0, "lstm_decode: temperature >= 0");
   TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, "lstm_decode: top_k >= 0 (0: off)");
   TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "lstm_decode: top_p in (0, 1] (1: off)");
   for (const optional<Tensor>* o : {&threshold, &logprobs})
-    if (present(*o)) TORCH_CHECK(f32(**o) && (*o)->dim() == 2 && (*o)->size(0) == B && (*o)->size(1) == N,
+    if (present(*o)) TORCH_CHECK(dev_f32(**o) && (*o)->dim() == 2 && (*o)->size(0) == B && (*o)->size(1) == N,
                                  "lstm_decode: threshold / logprobs [B, N] fp32, contiguous, on the device");
   PdrnnLstmDecodeArgs a{};
-  a.emb = emb.data_ptr();
-  a.w_ih = pi.data();
-  a.w_hh = ph.data();
-  a.bias = pb.data();
-  a.w_fc = w_fc.data_ptr();
-  a.b_fc = opt_ptr(b_fc);
-  a.h = h.data_ptr();
-  a.c = c.data_ptr<float>();
-  a.scratch = scratch.data_ptr<float>();
-  a.first = first.data_ptr<int64_t>();
+  a.stack = d.stack;
   a.forced = present(forced) ? forced->data_ptr<int64_t>() : nullptr;
   a.tokens = tokens.data_ptr<int64_t>();
-  a.logits = present(logits) ? logits->data_ptr<float>() : nullptr;
-  a.B = (int)B; a.H = (int)H; a.E = (int)E; a.V = (int)V; a.L = (int)L;
-  a.dtype = dt;
   a.temperature = (float)temperature;
   a.seed = (uint32_t)seed;
   a.stream0 = (uint32_t)stream0;
   a.pos0 = (uint32_t)pos0;
   a.top_k = (int)top_k;
   a.top_p = (float)top_p;
-  a.threshold = present(threshold) ? threshold->data_ptr<float>() : nullptr;
-  a.logprobs = present(logprobs) ? logprobs->data_ptr<float>() : nullptr;
+  a.threshold = opt_mut(threshold);
+  a.logprobs = opt_mut(logprobs);
   HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
 }
 
@@ -1872,77 +1902,40 @@ void lstm_decode_beam(const Tensor& emb, const std::vector<Tensor>& w_ih, const 
                       const Tensor& c, const Tensor& scratch, const Tensor& first, const Tensor& cum, const Tensor& done,
                       const Tensor& tokens, const Tensor& parents, const optional<Tensor>& lp,
                       const optional<Tensor>& logits, const Tensor& hyp, const optional<Tensor>& hyp_lp, int64_t G,
-                      int64_t W, int64_t stop, bool select_launch) {
+                      int64_t W, int64_t stop) {
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
-  const int dt = dtype_code(emb);
-  const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
-  TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
-              "lstm_decode_beam: emb [V, E], one w_ih / w_hh / bias per layer");
-  TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
-              "lstm_decode_beam: h [2, L, S, H] in the weights' dtype");
-  const int64_t S = h.size(2), H = h.size(3), N = tokens.dim() == 2 ? tokens.size(1) : 0;
+  const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
+  const DecodeStack d =
+      check_decode_stack("lstm_decode_beam", emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+  const PdrnnLstmDecodeStack& s = d.stack;
+  const int64_t S = s.B;
   TORCH_CHECK(G >= 1 && W >= 1 && G <= 16 && W <= 16 && G * W == S &&
-              pdrnn_lstm_decode_beam_supported((int)G, (int)W, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
-              "lstm_decode_beam: unsupported shape G=", G, " W=", W, " S=", S, " H=", H, " E=", E, " V=", V, " L=", L,
-              " N=", N);
-  TORCH_CHECK(stop >= -1 && stop < V, "lstm_decode_beam: stop in [0, V), or -1 for none");
-  auto aligned = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
-  auto f32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); };
-  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
-  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+              pdrnn_lstm_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype),
+              "lstm_decode_beam: unsupported shape G=", G, " W=", W, " S=", S, " H=", s.H, " E=", s.E, " V=", s.V,
+              " L=", s.L, " N=", N);
+  TORCH_CHECK(stop >= -1 && stop < s.V, "lstm_decode_beam: stop in [0, V), or -1 for none");
   auto sn = [&](const Tensor& t) { return t.dim() == 2 && t.size(0) == S && t.size(1) == N; };
-  std::vector<const void*> pi(L), ph(L);
-  std::vector<const float*> pb(L);
-  for (int64_t l = 0; l < L; ++l) {
-    const int64_t I = l == 0 ? E : H;
-    TORCH_CHECK(w_ih[l].is_cuda() && w_ih[l].is_contiguous() && dtype_code(w_ih[l]) == dt && w_ih[l].dim() == 2 &&
-                w_ih[l].size(0) == 4 * H && w_ih[l].size(1) == I && aligned(w_ih[l]), "lstm_decode_beam: w_ih [4H, I]");
-    TORCH_CHECK(w_hh[l].is_cuda() && w_hh[l].is_contiguous() && dtype_code(w_hh[l]) == dt && w_hh[l].dim() == 2 &&
-                w_hh[l].size(0) == 4 * H && w_hh[l].size(1) == H && aligned(w_hh[l]), "lstm_decode_beam: w_hh [4H, H]");
-    TORCH_CHECK(f32(bias[l]) && bias[l].numel() == 4 * H, "lstm_decode_beam: bias [4H] fp32");
-    pi[l] = w_ih[l].data_ptr();
-    ph[l] = w_hh[l].data_ptr();
-    pb[l] = bias[l].data_ptr<float>();
-  }
-  TORCH_CHECK(w_fc.is_cuda() && w_fc.is_contiguous() && dtype_code(w_fc) == dt && w_fc.dim() == 2 && w_fc.size(0) == V &&
-              w_fc.size(1) == H && aligned(w_fc) && aligned(emb) && aligned(h), "lstm_decode_beam: w_fc [V, H]");
-  if (present(b_fc)) TORCH_CHECK(f32(*b_fc) && b_fc->numel() == V, "lstm_decode_beam: b_fc [V] fp32");
-  TORCH_CHECK(f32(c) && c.numel() == L * S * H, "lstm_decode_beam: c [L, S, H] fp32");
-  TORCH_CHECK(f32(scratch) && scratch.numel() == S * V, "lstm_decode_beam: scratch [S, V] fp32");
-  TORCH_CHECK(i64(first) && first.numel() == S, "lstm_decode_beam: first [S] int64");
-  TORCH_CHECK(f32(cum) && cum.dim() == 2 && cum.size(0) == N + 1 && cum.size(1) == S, "lstm_decode_beam: cum [N + 1, S] fp32");
-  TORCH_CHECK(i32(done) && done.dim() == 2 && done.size(0) == N + 1 && done.size(1) == S,
+  TORCH_CHECK(dev_f32(cum) && cum.dim() == 2 && cum.size(0) == N + 1 && cum.size(1) == S,
+              "lstm_decode_beam: cum [N + 1, S] fp32");
+  TORCH_CHECK(dev_i32(done) && done.dim() == 2 && done.size(0) == N + 1 && done.size(1) == S,
               "lstm_decode_beam: done [N + 1, S] int32");
-  TORCH_CHECK(i64(tokens) && sn(tokens) && i64(hyp) && sn(hyp), "lstm_decode_beam: tokens / hyp [S, N] int64");
-  TORCH_CHECK(i32(parents) && sn(parents), "lstm_decode_beam: parents [S, N] int32");
+  TORCH_CHECK(dev_i64(tokens) && sn(tokens) && dev_i64(hyp) && sn(hyp), "lstm_decode_beam: tokens / hyp [S, N] int64");
+  TORCH_CHECK(dev_i32(parents) && sn(parents), "lstm_decode_beam: parents [S, N] int32");
   for (const optional<Tensor>* o : {&lp, &hyp_lp})
-    if (present(*o)) TORCH_CHECK(f32(**o) && sn(**o), "lstm_decode_beam: lp / hyp_lp [S, N] fp32");
+    if (present(*o)) TORCH_CHECK(dev_f32(**o) && sn(**o), "lstm_decode_beam: lp / hyp_lp [S, N] fp32");
   TORCH_CHECK(!present(hyp_lp) || present(lp), "lstm_decode_beam: hyp_lp needs lp");
-  if (present(logits)) TORCH_CHECK(f32(*logits) && logits->numel() == S * N * V, "lstm_decode_beam: logits [S, N, V] fp32");
   PdrnnLstmDecodeBeamArgs a{};
-  a.emb = emb.data_ptr();
-  a.w_ih = pi.data();
-  a.w_hh = ph.data();
-  a.bias = pb.data();
-  a.w_fc = w_fc.data_ptr();
-  a.b_fc = opt_ptr(b_fc);
-  a.h = h.data_ptr();
-  a.c = c.data_ptr<float>();
-  a.scratch = scratch.data_ptr<float>();
-  a.first = first.data_ptr<int64_t>();
+  a.stack = s;
   a.cum = cum.data_ptr<float>();
   a.done = done.data_ptr<int32_t>();
   a.tokens = tokens.data_ptr<int64_t>();
   a.parents = parents.data_ptr<int32_t>();
-  a.lp = present(lp) ? lp->data_ptr<float>() : nullptr;
-  a.logits = present(logits) ? logits->data_ptr<float>() : nullptr;
+  a.lp = opt_mut(lp);
   a.hyp = hyp.data_ptr<int64_t>();
-  a.hyp_lp = present(hyp_lp) ? hyp_lp->data_ptr<float>() : nullptr;
-  a.G = (int)G; a.W = (int)W; a.H = (int)H; a.E = (int)E; a.V = (int)V; a.L = (int)L;
-  a.dtype = dt;
+  a.hyp_lp = opt_mut(hyp_lp);
+  a.G = (int)G; a.W = (int)W;
   a.stop = (int)stop;
-  a.select_launch = select_launch ? 1 : 0;
   HIP_LAUNCH_CHECK(pdrnn_lstm_decode_beam(&a, (int)N, cur_stream()));
 }
 
@@ -1966,9 +1959,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> lstm_decode_beam_select(
   if (out.has_value()) {
     TORCH_CHECK(out->size() == 5, "lstm_decode_beam_select: out = (tokens, parents, lp, cum, done)");
     tokens = (*out)[0]; parents = (*out)[1]; lp = (*out)[2]; cum2 = (*out)[3]; done2 = (*out)[4];
-    auto ok = [&](const Tensor& t, at::ScalarType ty, int64_t n) {
-      return t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.numel() == n;
-    };
+    auto ok = [](const Tensor& t, at::ScalarType ty, int64_t n) { return dev_of(t, ty) && t.numel() == n; };
     TORCH_CHECK(ok(tokens, at::kLong, S) && ok(parents, at::kInt, S) && ok(lp, at::kFloat, S) &&
                 ok(cum2, at::kFloat, 2 * S) && ok(done2, at::kInt, 2 * S), "lstm_decode_beam_select: out buffers");
   } else {
@@ -2202,7 +2193,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
         py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("cum"), py::arg("done"),
         py::arg("tokens"), py::arg("parents"), py::arg("lp"), py::arg("logits"), py::arg("hyp"), py::arg("hyp_lp"),
-        py::arg("G"), py::arg("W"), py::arg("stop") = -1, py::arg("select_launch") = false);
+        py::arg("G"), py::arg("W"), py::arg("stop") = -1);
   m.def("lstm_decode_beam_supported",
         [](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
           auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };

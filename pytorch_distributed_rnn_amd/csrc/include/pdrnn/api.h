@@ -482,11 +482,7 @@ hipError_t pdrnn_slab_reduce_adam(const PdrnnAdamArgs* a, const float* A, int64_
 // ---- char-LM generation (kernels/lstm_decode.hip) --------------------------
 // One token of a unidirectional 16-bit LSTM stack with biases for B <= 16
 // streams is L launches of the decode layer kernel plus one of the vocabulary
-// head; position p's input token is forced[b, p] if forced is given, else
-// first[b] at p = 0, else the token sampled from position p - 1's logits
-// (pdrnn/decode_rng.h; temperature 0: their argmax).  tokens[b, p] always
-// receives the token sampled from position p's logits.  The hash sees stream
-// stream0 + b and position pos0 + p.
+// head.  The stack and its working buffers, common to sampling and beam search:
 typedef struct {
   const void* emb;           // [V, E] embedding, 16-bit
   const void* const* w_ih;   // host array [L]: [4H, E] (layer 0) / [4H, H], gate-interleaved rows 4u + q, 16-bit
@@ -497,12 +493,21 @@ typedef struct {
   void* h;                   // [2, L, B, H] 16-bit: h entering position p in slot p & 1, leaving it in the other
   float* c;                  // [L, B, H], updated in place
   float* scratch;            // [B, V] the latest position's logits
-  const int64_t* first;      // [B]
+  const int64_t* first;      // [B] position 0's input tokens
+  float* logits;             // [B, n_tokens, V] or NULL: per stream and position
+  int B, H, E, V, L;         // B: the streams of the launch (the search's G W)
+  int dtype;                 // 0 bf16, 1 fp16
+} PdrnnLstmDecodeStack;
+
+// Sampling: position p's input token is forced[b, p] if forced is given, else
+// first[b] at p = 0, else the token sampled from position p - 1's logits
+// (pdrnn/decode_rng.h; temperature 0: their argmax).  tokens[b, p] always
+// receives the token sampled from position p's logits.  The hash sees stream
+// stream0 + b and position pos0 + p.
+typedef struct {
+  PdrnnLstmDecodeStack stack;
   const int64_t* forced;     // [B, n_tokens] or NULL
   int64_t* tokens;           // [B, n_tokens]
-  float* logits;             // [B, n_tokens, V] or NULL
-  int B, H, E, V, L;
-  int dtype;                 // 0 bf16, 1 fp16
   float temperature;
   uint32_t seed, stream0, pos0;
   // the sampling filters and their outputs (pdrnn/decode_rng.h: the rule); all zero: off / not wanted
@@ -523,33 +528,22 @@ hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStre
 // (on position q's logits) runs inside the layer-0 launch of position q + 1,
 // the last one in a launch of its own that also traces the parents back.
 typedef struct {
-  const void* emb;           // as PdrnnLstmDecodeArgs, B = S
-  const void* const* w_ih;
-  const void* const* w_hh;
-  const float* const* bias;
-  const void* w_fc;
-  const float* b_fc;
-  void* h;                   // [2, L, S, H]: a group's W streams all start from the prompt's state
-  float* c;                  // [L, S, H], in place
-  float* scratch;            // [S, V]
-  const int64_t* first;      // [S] the prompt's last token, W times per group
+  PdrnnLstmDecodeStack stack;  // B = S: a group's W streams all start from the prompt's state (h, c) and
+                               // last token (first, W times per group)
   float* cum;                // [n_tokens + 1, S]: row 0 the caller's start scores (0, -inf, ... per group),
   int32_t* done;             // [n_tokens + 1, S]: row 0 the caller's (zeros); row q + 1 written by selection q
   int64_t* tokens;           // [S, n_tokens] the token slot s took at selection q,
   int32_t* parents;          // [S, n_tokens] the stream it continues,
   float* lp;                 // [S, n_tokens] or NULL: and that token's log-prob (0 for a done beam's stop)
-  float* logits;             // [S, n_tokens, V] or NULL: per slot and position
   int64_t* hyp;              // [S, n_tokens] the hypotheses in final rank order
   float* hyp_lp;             // [S, n_tokens] or NULL (needs lp): the log-probs along each
-  int G, W, H, E, V, L;
-  int dtype;                 // 0 bf16, 1 fp16
+  int G, W;
   int stop;                  // -1: none
-  int select_launch;         // 1: every selection a one-workgroup launch of its own (measurement)
 } PdrnnLstmDecodeBeamArgs;
 // the decode limits at B = G W, 1 <= W <= 16, G W <= 16
 int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype);
 // Enqueues (L + 1) * n_tokens launches and the last selection; no host read.
-// Bad arguments (a shape not supported, n_tokens < 1, stop outside [-1, V)) are hipErrorInvalidValue.
+// Bad arguments (a shape not supported, stack.B != G W, n_tokens < 1, stop outside [-1, V)) are hipErrorInvalidValue.
 hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream);
 // ONE selection through the last position's kernel: logits [S, V], cum / done
 // [2, S] (row 0 read, row 1 written), tokens / parents / lp [S].

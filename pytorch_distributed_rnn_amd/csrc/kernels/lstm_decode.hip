@@ -5,7 +5,7 @@
 // the weights (about 28 MB at 2 x 1024, resident in the Infinity Cache), and
 // the training kernels' 256-row tiles and per-step host work are all overhead.
 // Here a token is L + 1 short launches on one stream and nothing else:
-//   * lstm_decode_layer<DT, FIRST>: [x_t | h_{t-1}] [W_ih | W_hh]^T on
+//   * lstm_decode_layer<DT, FIRST, PICK>: [x_t | h_{t-1}] [W_ih | W_hh]^T on
 //     v_mfma_f32_16x16x32 with the WEIGHTS as the A operand and the streams,
 //     padded to 16, as B.  A workgroup owns 16 gate-interleaved rows (4 hidden
 //     units); its 8 waves split K and reduce through LDS.  In the accumulator
@@ -18,19 +18,21 @@
 //     reads x_t straight from that row of the 16-bit embedding.  Every
 //     workgroup samples the same B tokens on its own (B x V values, an argmax);
 //     workgroup 0 alone records them.  With a top-k / nucleus filter or the
-//     log-probs wanted, the FILT instantiation first finds each row's keep
-//     threshold by a bitwise selection in registers (sample_tokens_filtered).
+//     log-probs wanted, the Pick::filtered instantiation first finds each row's
+//     keep threshold by a bitwise selection in registers (sample_tokens_filtered_n).
 //   * lstm_decode_head<DT>: logits = h_top W_fc^T + b_fc in fp32, 16
 //     vocabulary rows per workgroup, rows past V masked.
-//   * Beam search (the BEAM instantiations; pdrnn/decode_rng.h: the rule): G
-//     groups of W beams are G W <= 16 of the streams.  In sampling's place
-//     layer 0 selects each group's W best of its W V candidates (beam_select)
-//     and every layer reads h_{t-1} and c of stream parent[n] instead of n;
-//     the last selection and the backtrace are lstm_decode_beam_pick.
+//   * Beam search (the Pick::beam instantiations; pdrnn/decode_rng.h: the
+//     rule): G groups of W beams are G W <= 16 of the streams.  In sampling's
+//     place layer 0 selects each group's W best of its W V candidates
+//     (beam_select_n) and every layer reads h_{t-1} and c of stream parent[n]
+//     instead of n; the last selection and the backtrace are lstm_decode_beam_pick.
 // h ping-pongs between two buffers by token parity (every workgroup reads all
 // of h_{t-1} while the others write h_t); layer l > 0 reads layer l - 1's h_t
 // of the same token.  All ordering is kernel boundaries on one stream: nothing
-// inside a launch waits for another workgroup.
+// inside a launch waits for another workgroup.  Sampling and the search share
+// one token loop on the host (decode_positions) and differ in the layer-0
+// instantiation and in the launch after the last position.
 //
 // Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) +
 // nn.Linear stepped one token at a time.
@@ -74,7 +76,7 @@ struct SampleArgs {
   int B, V, N;
   float temperature;      // 0: greedy
   uint32_t seed, stream0, pos0;
-  // the filtered sampler only (sample_tokens_filtered)
+  // the filtered sampler only (sample_tokens_filtered_n)
   int top_k;              // 0: off
   float top_p;            // 0 or >= 1: off
   float* threshold;       // [B, N] or null
@@ -83,7 +85,9 @@ struct SampleArgs {
 
 // tok[b] = argmax_v(logit / T + g), the lowest index on ties, for every stream
 // b < B; position p of the N generated ones (hash position pos0 + p).  Wave w
-// takes streams w, w + 8, ...; all lanes of the workgroup must call.
+// takes streams w, w + 8, ...; all lanes of the workgroup must call.  (The draw
+// stands here and again in sample_tokens_filtered_n, as it was: written once as
+// a shared helper it changed the filtered kernels' code, profiles/r16/decode_refactor.md.)
 __device__ __forceinline__ void sample_tokens(const SampleArgs& s, int p, int* tok) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int b = wave; b < s.B; b += kWaves) {
@@ -109,48 +113,100 @@ __device__ __forceinline__ void sample_tokens(const SampleArgs& s, int p, int* t
   }
 }
 
+// Thread b < B records stream b's token (threshold, log-prob) at column p.
+template <bool FILT>
+__device__ __forceinline__ void record_sample(const SampleArgs& s, int p, const int* tok, const float* thr,
+                                              const float* lp) {
+  if (threadIdx.x < s.B) {
+    const int64_t at = (int64_t)threadIdx.x * s.N + p;
+    s.tokens[at] = tok[threadIdx.x];
+    if constexpr (FILT) {
+      if (s.threshold != nullptr) s.threshold[at] = thr[threadIdx.x];
+      if (s.logprobs != nullptr) s.logprobs[at] = lp[threadIdx.x];
+    }
+  }
+}
+
+// a token held inside the vocabulary: a bad value reads no memory outside the embedding
+__device__ __forceinline__ int64_t clamp_token(int64_t t, int V) {
+  PDRNN_DEVICE_ASSERT(t >= 0 && t < V);
+  return t < 0 ? 0 : (t >= V ? V - 1 : t);
+}
+
 constexpr int kSlots = 16;  // logits a lane holds at the most: ceil(1024 / 64)
 
-// x (op) the value of another lane of the row of 16, by a DPP control
-template <int CTRL>
-__device__ __forceinline__ float dpp_peer(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float lane_value(float x, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
-}
-
-// Wave-wide sum in a fixed order, no LDS path.  Within a row of 16 lanes a
-// butterfly: the lanes paired at a stage add the same two values (a + b and
-// b + a: the same bits), so the row's lanes end equal -- quad_perm [1 0 3 2],
-// [2 3 0 1], then row_half_mirror and row_mirror, which pair a lane with one of
-// the other, already equal, quad or half.  The four row sums are then read out
-// and added as (r0 + r1) + (r2 + r3) in every lane.  Every wave of every
-// workgroup that starts from the same row ends with the same bits.
-__device__ __forceinline__ float wave_sum(float x) {
-  x += dpp_peer<0xb1>(x);
-  x += dpp_peer<0x4e>(x);
-  x += dpp_peer<0x141>(x);
-  x += dpp_peer<0x140>(x);
-  return (lane_value(x, 0) + lane_value(x, 16)) + (lane_value(x, 32) + lane_value(x, 48));
+// f(Slots<NS>): NS the slots a lane needs for a row of V (the launch's: V is uniform)
+template <int NS>
+struct Slots {
+  static constexpr int value = NS;
+};
+template <class F>
+__device__ __forceinline__ void with_slots(int V, F&& f) {
+  if (V <= 1 * kWave) f(Slots<1>{});
+  else if (V <= 2 * kWave) f(Slots<2>{});
+  else if (V <= 4 * kWave) f(Slots<4>{});
+  else if (V <= 8 * kWave) f(Slots<8>{});
+  else f(Slots<kSlots>{});
 }
 
-__device__ __forceinline__ float wave_max(float x) {
-  x = fmaxf(x, dpp_peer<0xb1>(x));
-  x = fmaxf(x, dpp_peer<0x4e>(x));
-  x = fmaxf(x, dpp_peer<0x141>(x));
-  x = fmaxf(x, dpp_peer<0x140>(x));
-  return fmaxf(fmaxf(lane_value(x, 0), lane_value(x, 16)), fmaxf(lane_value(x, 32), lane_value(x, 48)));
+// A lane's entries lane, lane + 64, ... of a row of V: every load in flight at
+// once, the index held inside the row.  The slots past V hold a copy of the
+// last entry: the caller sets them to -inf where it first reads the values
+// (masking here instead cost the filtered sampler a select per slot and beam
+// layer 0 four VGPRs, profiles/r16/decode_resources.md).
+template <int NS>
+__device__ __forceinline__ void load_row(const float* row, int V, float (&l)[NS]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int v = lane + i * kWave;
+    l[i] = row[v < V ? v : V - 1];
+  }
 }
 
-// sum{w : key >= t}: a lane's slots in order, then wave_sum.  The terms are
-// >= 0 and rounding is monotone, so the sum does not grow with t.
+// The value of another lane of the row of 16, by a DPP control; of any lane of the wave.
+template <int CTRL, class T>
+__device__ __forceinline__ T dpp_peer(T x) {
+  return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
+}
+template <class T>
+__device__ __forceinline__ T lane_value(T x, int lane) {
+  return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
+}
+
+struct Sum {
+  static __device__ __forceinline__ float op(float a, float b) { return a + b; }
+};
+struct Max {
+  static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
+  static __device__ __forceinline__ uint32_t op(uint32_t a, uint32_t b) { return a > b ? a : b; }
+};
+
+// Wave-wide reduction in a fixed order, no LDS path.  Within a row of 16 lanes
+// a butterfly: the lanes paired at a stage combine the same two values (a + b
+// and b + a: the same bits), so the row's lanes end equal -- quad_perm
+// [1 0 3 2], [2 3 0 1], then row_half_mirror and row_mirror, which pair a lane
+// with one of the other, already equal, quad or half.  The four row values are
+// then read out and combined as (r0 + r1) + (r2 + r3) in every lane.  Every
+// wave of every workgroup that starts from the same row ends with the same
+// bits: with Sum that is what makes all of them find the same threshold and token.
+template <class Op, class T>
+__device__ __forceinline__ T wave_reduce(T x) {
+  x = Op::op(x, dpp_peer<0xb1>(x));
+  x = Op::op(x, dpp_peer<0x4e>(x));
+  x = Op::op(x, dpp_peer<0x141>(x));
+  x = Op::op(x, dpp_peer<0x140>(x));
+  return Op::op(Op::op(lane_value(x, 0), lane_value(x, 16)), Op::op(lane_value(x, 32), lane_value(x, 48)));
+}
+
+// sum{w : key >= t}: a lane's slots in order, then the wave's sum.  The terms
+// are >= 0 and rounding is monotone, so the sum does not grow with t.
 template <int NS>
 __device__ __forceinline__ float mass_at_least(const uint32_t (&key)[NS], const float (&w)[NS], uint32_t t) {
   float acc = 0.f;
 #pragma unroll
   for (int i = 0; i < NS; ++i) acc += key[i] >= t ? w[i] : 0.f;
-  return wave_sum(acc);
+  return wave_reduce<Sum>(acc);
 }
 
 // |{key >= t}|, t > 0 (slots past V hold key 0)
@@ -187,11 +243,7 @@ __device__ __forceinline__ void sample_tokens_filtered_n(const SampleArgs& s, in
     const float* row = s.scratch + (int64_t)b * V;
     float l[NS], w[NS];
     uint32_t key[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {  // every load in flight at once: the index held inside the row
-      const int v = lane + i * kWave;
-      l[i] = row[v < V ? v : V - 1];
-    }
+    load_row<NS>(row, V, l);
     float m = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
@@ -202,7 +254,7 @@ __device__ __forceinline__ void sample_tokens_filtered_n(const SampleArgs& s, in
       w[i] = 0.f;
     }
     if (mass) {
-      m = wave_max(m);
+      m = wave_reduce<Max>(m);
 #pragma unroll
       for (int i = 0; i < NS; ++i) w[i] = expf(l[i] / T - m);  // (slots past V: exp(-inf) = 0)
     }
@@ -251,7 +303,7 @@ __device__ __forceinline__ void sample_tokens_filtered_n(const SampleArgs& s, in
       float acc = 0.f;
 #pragma unroll
       for (int i = 0; i < NS; ++i) acc += l[i] >= tau ? w[i] : 0.f;
-      lpv = row[bi] / T - m - logf(wave_sum(acc));
+      lpv = row[bi] / T - m - logf(wave_reduce<Sum>(acc));
     }
     if (lane == 0) {
       tok[b] = bi;
@@ -261,13 +313,11 @@ __device__ __forceinline__ void sample_tokens_filtered_n(const SampleArgs& s, in
   }
 }
 
-// (the slot count is the launch's: V is uniform)
-__device__ __forceinline__ void sample_tokens_filtered(const SampleArgs& s, int p, int* tok, float* thr, float* lp) {
-  if (s.V <= 1 * kWave) sample_tokens_filtered_n<1>(s, p, tok, thr, lp);
-  else if (s.V <= 2 * kWave) sample_tokens_filtered_n<2>(s, p, tok, thr, lp);
-  else if (s.V <= 4 * kWave) sample_tokens_filtered_n<4>(s, p, tok, thr, lp);
-  else if (s.V <= 8 * kWave) sample_tokens_filtered_n<8>(s, p, tok, thr, lp);
-  else sample_tokens_filtered_n<kSlots>(s, p, tok, thr, lp);
+// The workgroup's sampling of position p: tok (thr, lp) [B] in LDS.
+template <bool FILT>
+__device__ __forceinline__ void sample_position(const SampleArgs& s, int p, int* tok, float* thr, float* lp) {
+  if constexpr (FILT) with_slots(s.V, [&](auto ns) { sample_tokens_filtered_n<decltype(ns)::value>(s, p, tok, thr, lp); });
+  else sample_tokens(s, p, tok);
 }
 
 // ---- beam search (pdrnn/decode_rng.h: the rule) -------------------------------
@@ -283,7 +333,6 @@ struct BeamArgs {
   float* lp;             // [S, N] or null
   int G, W, V, N;
   int stop;              // -1: none
-  int separate;          // the selection is a launch of its own: layer 0 reads tokens / parents
 };
 
 struct BeamLds {
@@ -293,22 +342,6 @@ struct BeamLds {
   int parent[kStreams], tok[kStreams], done[kStreams];  // the new slots
   float cum[kStreams], lp[kStreams];
 };
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_peer_u(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t lane_value_u(uint32_t x, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)x, lane);
-}
-__device__ __forceinline__ uint32_t wave_umax(uint32_t x) {
-  x = umax(x, dpp_peer_u<0xb1>(x));
-  x = umax(x, dpp_peer_u<0x4e>(x));
-  x = umax(x, dpp_peer_u<0x141>(x));
-  x = umax(x, dpp_peer_u<0x140>(x));
-  return umax(umax(lane_value_u(x, 0), lane_value_u(x, 16)), umax(lane_value_u(x, 32), lane_value_u(x, 48)));
-}
 
 // One selection, by every lane of the workgroup; the new slots end in L.
 //   1. A wave per stream, the row in registers as in sample_tokens_filtered_n:
@@ -331,25 +364,21 @@ __device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds&
     const bool ds = done[s] != 0;
     float l[NS], lpv[NS];
     uint32_t key[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int v = lane + i * kWave;
-      l[i] = row[v < V ? v : V - 1];
-    }
+    load_row<NS>(row, V, l);
     float m = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       if (lane + i * kWave >= V) l[i] = -INFINITY;
       m = fmaxf(m, l[i]);
     }
-    m = wave_max(m);
+    m = wave_reduce<Max>(m);
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       l[i] -= m;
       acc += lane + i * kWave < V ? expf(l[i]) : 0.f;
     }
-    const float lse = logf(wave_sum(acc));
+    const float lse = logf(wave_reduce<Sum>(acc));
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       const int v = lane + i * kWave;
@@ -361,8 +390,8 @@ __device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds&
     for (int r = 0; r < W; ++r) {
       uint32_t mx = 0;
 #pragma unroll
-      for (int i = 0; i < NS; ++i) mx = umax(mx, key[i]);
-      mx = wave_umax(mx);
+      for (int i = 0; i < NS; ++i) mx = Max::op(mx, key[i]);
+      mx = wave_reduce<Max>(mx);
       int wv = 0;
       float wl = 0.f;
       if (mx != 0) {
@@ -393,7 +422,7 @@ __device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds&
 #pragma unroll 1
     for (int i = 0; i < W; ++i) {
       const uint32_t k = lane < W && head < W ? L.ck[s][head] : 0;
-      const uint32_t mx = wave_umax(k);
+      const uint32_t mx = wave_reduce<Max>(k);
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(lane < W && k == mx);
       const int j = __builtin_ctzll(bal);  // (a group always has W candidates: lane 0 at the worst)
       PDRNN_DEVICE_ASSERT(mx != 0);
@@ -412,11 +441,7 @@ __device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds&
 }
 
 __device__ __forceinline__ void beam_select(const BeamArgs& b, int q, BeamLds& L) {
-  if (b.V <= 1 * kWave) beam_select_n<1>(b, q, L);
-  else if (b.V <= 2 * kWave) beam_select_n<2>(b, q, L);
-  else if (b.V <= 4 * kWave) beam_select_n<4>(b, q, L);
-  else if (b.V <= 8 * kWave) beam_select_n<8>(b, q, L);
-  else beam_select_n<kSlots>(b, q, L);
+  with_slots(b.V, [&](auto ns) { beam_select_n<decltype(ns)::value>(b, q, L); });
 }
 
 // selection q's record (one workgroup's job)
@@ -450,8 +475,12 @@ struct LayerArgs {
   const int64_t* forced;  // FIRST: [B, N] input tokens of every position, or null
   SampleArgs s;
   int H, Kx, p;
-  BeamArgs b;             // BEAM: the search (s: B, V and N only)
+  BeamArgs b;             // Pick::beam: the search (s: B, V and N only)
 };
+
+// How position p's input token is chosen in layer 0.  The layers above read
+// only "beam or not" from it: they exist for sample and beam.
+enum class Pick { sample, filtered, beam };
 
 // Sum of the waves' partial accumulators, in wave order, into wave 0.
 __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
@@ -464,20 +493,25 @@ __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
   return sum;
 }
 
-// FILT (layer 0 only, chosen on the host): the filtered sampler and its two
-// outputs; a launch sequence with no filter and no output wanted never runs it.
+// Pick::filtered (layer 0 only, chosen on the host): the filtered sampler and
+// its two outputs; a launch sequence with no filter and no output wanted never
+// runs it.
 //
-// BEAM: stream n continues stream par = parent[n] of the previous position: it
-// reads h_{t-1} and c of par in every layer (x of a layer above 0 is the layer
-// below's h_t, already in new-slot order).  Layer 0 selects (beam_select; by
-// every workgroup, recorded by workgroup 0) or, with the selection a launch of
-// its own, reads that launch's record; the layers above read the record.  c
-// stays in place: a unit's 16 streams are 16 lanes of wave 0 of one workgroup,
-// which loads c[par] in one instruction and stores c[n] in a later one that
-// depends on the loaded value, so every lane's load has completed before any
-// lane's store; no other workgroup touches the unit.
-template <class DT, bool FIRST, bool FILT = false, bool BEAM = false>
+// Pick::beam: stream n continues stream par = parent[n] of the previous
+// position: it reads h_{t-1} and c of par in every layer (x of a layer above 0
+// is the layer below's h_t, already in new-slot order).  Layer 0 selects
+// (beam_select; by every workgroup, recorded by workgroup 0); the layers above
+// read the record.  c stays in place: a unit's 16 streams are 16 lanes of wave
+// 0 of one workgroup, which loads c[par] in one instruction and stores c[n] in
+// a later one that depends on the loaded value, so every lane's load has
+// completed before any lane's store; no other workgroup touches the unit.
+//
+// Every __syncthreads() below is reached by all threads of a workgroup: what
+// guards the sampling and the selection (p, forced, blockIdx) is uniform in it.
+template <class DT, bool FIRST, Pick PICK>
 __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a) {
+  static_assert(FIRST || PICK != Pick::filtered, "the filter is layer 0's");
+  constexpr bool FILT = PICK == Pick::filtered, BEAM = PICK == Pick::beam;
   __shared__ f32x4 red[kWaves][kWave];
   __shared__ int tok[kStreams];
   __shared__ float thr[FILT ? kStreams : 1], lp[FILT ? kStreams : 1];
@@ -490,18 +524,15 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   const uint16_t* xrow = a.x + (int64_t)n * Kx;  // (read only where live)
   if constexpr (BEAM && FIRST) {
     __shared__ BeamLds L;
-    const bool select = a.p > 0 && !a.b.separate;
-    if (select) {
+    if (a.p > 0) {
       beam_select(a.b, a.p - 1, L);
       if (blockIdx.x == 0) beam_record(a.b, a.p - 1, L);
     }
     int64_t t = 0;
     if (live) {
       if (a.p == 0) t = a.first[n];
-      else if (select) t = L.tok[n], par = L.parent[n];
-      else t = a.b.tokens[(int64_t)n * a.b.N + a.p - 1], par = a.b.parents[(int64_t)n * a.b.N + a.p - 1];
-      PDRNN_DEVICE_ASSERT(t >= 0 && t < a.s.V);
-      t = t < 0 ? 0 : (t >= a.s.V ? a.s.V - 1 : t);
+      else t = L.tok[n], par = L.parent[n];
+      t = clamp_token(t, a.s.V);
       par = beam_parent(par, n, a.b.W);
     }
     xrow = a.x + t * Kx;
@@ -511,26 +542,15 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
     // the sampled token is needed as an input only when nothing is forced;
     // forced runs still record it, which is workgroup 0's job alone
     const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
-    if (sample) {
-      if constexpr (FILT) sample_tokens_filtered(a.s, a.p - 1, tok, thr, lp);
-      else sample_tokens(a.s, a.p - 1, tok);
-    }
+    if (sample) sample_position<FILT>(a.s, a.p - 1, tok, thr, lp);
     __syncthreads();
-    if (sample && blockIdx.x == 0 && threadIdx.x < B) {
-      const int64_t at = (int64_t)threadIdx.x * a.s.N + a.p - 1;
-      a.s.tokens[at] = tok[threadIdx.x];
-      if constexpr (FILT) {
-        if (a.s.threshold != nullptr) a.s.threshold[at] = thr[threadIdx.x];
-        if (a.s.logprobs != nullptr) a.s.logprobs[at] = lp[threadIdx.x];
-      }
-    }
+    if (sample && blockIdx.x == 0) record_sample<FILT>(a.s, a.p - 1, tok, thr, lp);
     int64_t t = 0;
     if (live) {
       if (a.forced != nullptr) t = a.forced[(int64_t)n * a.s.N + a.p];
       else if (a.p == 0) t = a.first[n];
       else t = tok[n];
-      PDRNN_DEVICE_ASSERT(t >= 0 && t < a.s.V);
-      t = t < 0 ? 0 : (t >= a.s.V ? a.s.V - 1 : t);  // a token outside the vocabulary reads no memory outside it
+      t = clamp_token(t, a.s.V);
     }
     xrow = a.x + t * Kx;
   }
@@ -615,23 +635,14 @@ template <bool FILT>
 __global__ __launch_bounds__(kThreads) void lstm_decode_sample(const SampleArgs s) {
   __shared__ int tok[kStreams];
   __shared__ float thr[FILT ? kStreams : 1], lp[FILT ? kStreams : 1];
-  if constexpr (FILT) sample_tokens_filtered(s, s.N - 1, tok, thr, lp);
-  else sample_tokens(s, s.N - 1, tok);
+  sample_position<FILT>(s, s.N - 1, tok, thr, lp);
   __syncthreads();
-  if (threadIdx.x < s.B) {
-    const int64_t at = (int64_t)threadIdx.x * s.N + s.N - 1;
-    s.tokens[at] = tok[threadIdx.x];
-    if constexpr (FILT) {
-      if (s.threshold != nullptr) s.threshold[at] = thr[threadIdx.x];
-      if (s.logprobs != nullptr) s.logprobs[at] = lp[threadIdx.x];
-    }
-  }
+  record_sample<FILT>(s, s.N - 1, tok, thr, lp);
 }
 
-// Selection q as a launch of its own (one workgroup): after the last position,
-// and per position when the selection is kept out of the layer-0 launch.  hyp
-// != null (the last selection): the parents are then traced back, a thread per
-// final slot, into hyp [S, N] (and hyp_lp from lp), the last column from LDS.
+// Selection q as a launch of its own (one workgroup): the one after the last
+// position.  hyp != null: the parents are then traced back, a thread per final
+// slot, into hyp [S, N] (and hyp_lp from lp), the last column from LDS.
 __global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs b, int q, int64_t* hyp, float* hyp_lp) {
   __shared__ BeamLds L;
   beam_select(b, q, L);
@@ -647,92 +658,70 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs
   }
 }
 
-template <class DT>
-hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
-  const int S = a->G * a->W, H = a->H, E = a->E, V = a->V, L = a->L;
-  const BeamArgs b{a->scratch, a->cum, a->done, a->tokens, a->parents, a->lp, a->G, a->W, V, n_tokens,
-                   a->stop, a->select_launch != 0};
-  SampleArgs s{};
-  s.B = S;
-  s.V = V;
-  s.N = n_tokens;
-  const uint16_t* h = static_cast<const uint16_t*>(a->h);
-  uint16_t* hm = static_cast<uint16_t*>(a->h);
-  const int64_t BH = (int64_t)S * H, slot = (int64_t)L * BH;
+// The token loop of both modes: per position the layer-0 kernel of the mode,
+// the layers above and the head, L + 1 launches on the one stream.  k arrives
+// with the mode's part (s, b, forced) filled in; the caller enqueues the
+// mode's last launch.
+template <class DT, Pick PICK>
+hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, LayerArgs k, hipStream_t stream) {
+  constexpr Pick ABOVE = PICK == Pick::beam ? Pick::beam : Pick::sample;
+  const int B = a.B, H = a.H, V = a.V, L = a.L;
+  const uint16_t* h = static_cast<const uint16_t*>(a.h);
+  uint16_t* hm = static_cast<uint16_t*>(a.h);
+  const int64_t BH = (int64_t)B * H, slot = (int64_t)L * BH;
+  k.first = a.first;
+  k.H = H;
   for (int p = 0; p < n_tokens; ++p) {
-    const int64_t in = (p & 1) * slot, out = ((p + 1) & 1) * slot;
-    if (b.separate && p > 0) {
-      lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(b, p - 1, nullptr, nullptr);
-      PDRNN_HIP_CHECK(hipGetLastError());
-    }
+    const int64_t in = (p & 1) * slot, out = ((p + 1) & 1) * slot;  // h_{t-1} and h_t of every layer
+    k.p = p;
     for (int l = 0; l < L; ++l) {
-      LayerArgs k{};
-      k.wx = static_cast<const uint16_t*>(a->w_ih[l]);
-      k.wh = static_cast<const uint16_t*>(a->w_hh[l]);
-      k.bias = a->bias[l];
-      k.x = l == 0 ? static_cast<const uint16_t*>(a->emb) : h + out + (l - 1) * BH;
+      k.wx = static_cast<const uint16_t*>(a.w_ih[l]);
+      k.wh = static_cast<const uint16_t*>(a.w_hh[l]);
+      k.bias = a.bias[l];
+      k.x = l == 0 ? static_cast<const uint16_t*>(a.emb) : h + out + (l - 1) * BH;
       k.hprev = h + in + l * BH;
       k.hout = hm + out + l * BH;
-      k.c = a->c + l * BH;
-      k.first = a->first;
-      k.s = s;
-      k.H = H;
-      k.Kx = l == 0 ? E : H;
-      k.p = p;
-      k.b = b;
-      if (l == 0) lstm_decode_layer<DT, true, false, true><<<H / 4, kThreads, 0, stream>>>(k);
-      else lstm_decode_layer<DT, false, false, true><<<H / 4, kThreads, 0, stream>>>(k);
+      k.c = a.c + l * BH;
+      k.Kx = l == 0 ? a.E : H;
+      if (l == 0) lstm_decode_layer<DT, true, PICK><<<H / 4, kThreads, 0, stream>>>(k);
+      else lstm_decode_layer<DT, false, ABOVE><<<H / 4, kThreads, 0, stream>>>(k);
       PDRNN_HIP_CHECK(hipGetLastError());
     }
-    const HeadArgs hd{static_cast<const uint16_t*>(a->w_fc), a->b_fc, h + out + (L - 1) * BH, a->scratch, a->logits,
-                      S, H, V, n_tokens, p};
+    const HeadArgs hd{static_cast<const uint16_t*>(a.w_fc), a.b_fc, h + out + (L - 1) * BH, a.scratch, a.logits,
+                      B, H, V, n_tokens, p};
     lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
     PDRNN_HIP_CHECK(hipGetLastError());
   }
-  lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(b, n_tokens - 1, a->hyp, a->hyp_lp);
+  return hipSuccess;
+}
+
+template <class DT>
+hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
+  const PdrnnLstmDecodeStack& st = a->stack;
+  LayerArgs k{};
+  k.b = BeamArgs{st.scratch, a->cum, a->done, a->tokens, a->parents, a->lp, a->G, a->W, st.V, n_tokens, a->stop};
+  k.s.B = st.B;
+  k.s.V = st.V;
+  k.s.N = n_tokens;
+  PDRNN_HIP_CHECK((decode_positions<DT, Pick::beam>(st, n_tokens, k, stream)));
+  lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(k.b, n_tokens - 1, a->hyp, a->hyp_lp);
   return hipGetLastError();
 }
 
 template <class DT>
 hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
-  const int B = a->B, H = a->H, E = a->E, V = a->V, L = a->L;
-  const bool top_k = a->top_k > 0 && a->top_k < V, top_p = a->top_p > 0.f && a->top_p < 1.f;
+  const PdrnnLstmDecodeStack& st = a->stack;
+  const bool top_k = a->top_k > 0 && a->top_k < st.V, top_p = a->top_p > 0.f && a->top_p < 1.f;
   // the filtered sampler only where it has something to do: a filter at T > 0, or an output to fill
   const bool filt = (a->temperature != 0.f && (top_k || top_p)) || a->threshold != nullptr || a->logprobs != nullptr;
-  const SampleArgs s{a->scratch, a->tokens, B, V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0,
-                     top_k ? a->top_k : 0, top_p ? a->top_p : 0.f, a->threshold, a->logprobs};
-  const uint16_t* h = static_cast<const uint16_t*>(a->h);
-  uint16_t* hm = static_cast<uint16_t*>(a->h);
-  const int64_t BH = (int64_t)B * H, slot = (int64_t)L * BH;
-  for (int p = 0; p < n_tokens; ++p) {
-    const int64_t in = (p & 1) * slot, out = ((p + 1) & 1) * slot;  // h_{t-1} and h_t of every layer
-    for (int l = 0; l < L; ++l) {
-      LayerArgs k{};
-      k.wx = static_cast<const uint16_t*>(a->w_ih[l]);
-      k.wh = static_cast<const uint16_t*>(a->w_hh[l]);
-      k.bias = a->bias[l];
-      k.x = l == 0 ? static_cast<const uint16_t*>(a->emb) : h + out + (l - 1) * BH;
-      k.hprev = h + in + l * BH;
-      k.hout = hm + out + l * BH;
-      k.c = a->c + l * BH;
-      k.first = a->first;
-      k.forced = a->forced;
-      k.s = s;
-      k.H = H;
-      k.Kx = l == 0 ? E : H;
-      k.p = p;
-      if (l == 0 && filt) lstm_decode_layer<DT, true, true><<<H / 4, kThreads, 0, stream>>>(k);
-      else if (l == 0) lstm_decode_layer<DT, true><<<H / 4, kThreads, 0, stream>>>(k);
-      else lstm_decode_layer<DT, false><<<H / 4, kThreads, 0, stream>>>(k);
-      PDRNN_HIP_CHECK(hipGetLastError());
-    }
-    const HeadArgs hd{static_cast<const uint16_t*>(a->w_fc), a->b_fc, h + out + (L - 1) * BH, a->scratch, a->logits,
-                      B, H, V, n_tokens, p};
-    lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
-    PDRNN_HIP_CHECK(hipGetLastError());
-  }
-  if (filt) lstm_decode_sample<true><<<1, kThreads, 0, stream>>>(s);
-  else lstm_decode_sample<false><<<1, kThreads, 0, stream>>>(s);
+  LayerArgs k{};
+  k.s = SampleArgs{st.scratch, a->tokens, st.B, st.V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0,
+                   top_k ? a->top_k : 0, top_p ? a->top_p : 0.f, a->threshold, a->logprobs};
+  k.forced = a->forced;
+  PDRNN_HIP_CHECK(filt ? (decode_positions<DT, Pick::filtered>(st, n_tokens, k, stream))
+                       : (decode_positions<DT, Pick::sample>(st, n_tokens, k, stream)));
+  if (filt) lstm_decode_sample<true><<<1, kThreads, 0, stream>>>(k.s);
+  else lstm_decode_sample<false><<<1, kThreads, 0, stream>>>(k.s);
   return hipGetLastError();
 }
 
@@ -747,9 +736,10 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype) {
 }
 
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
-  if (n_tokens < 1 || !pdrnn_lstm_decode_supported(a->B, a->H, a->E, a->V, a->L, a->dtype)) return hipErrorInvalidValue;
+  const PdrnnLstmDecodeStack& st = a->stack;
+  if (n_tokens < 1 || !pdrnn_lstm_decode_supported(st.B, st.H, st.E, st.V, st.L, st.dtype)) return hipErrorInvalidValue;
   if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
-  return a->dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
+  return st.dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
 }
 
 int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype) {
@@ -758,11 +748,13 @@ int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, i
 }
 
 hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
-  if (n_tokens < 1 || !pdrnn_lstm_decode_beam_supported(a->G, a->W, a->H, a->E, a->V, a->L, a->dtype))
+  const PdrnnLstmDecodeStack& st = a->stack;
+  if (n_tokens < 1 || !pdrnn_lstm_decode_beam_supported(a->G, a->W, st.H, st.E, st.V, st.L, st.dtype) ||
+      st.B != a->G * a->W)
     return hipErrorInvalidValue;
-  if (a->stop < -1 || a->stop >= a->V || (a->hyp_lp != nullptr && a->lp == nullptr) || a->hyp == nullptr)
+  if (a->stop < -1 || a->stop >= st.V || (a->hyp_lp != nullptr && a->lp == nullptr) || a->hyp == nullptr)
     return hipErrorInvalidValue;
-  return a->dtype == 0 ? pdrnn::decode_beam<pdrnn::BF16>(a, n_tokens, stream)
+  return st.dtype == 0 ? pdrnn::decode_beam<pdrnn::BF16>(a, n_tokens, stream)
                        : pdrnn::decode_beam<pdrnn::F16>(a, n_tokens, stream);
 }
 
@@ -772,7 +764,7 @@ hipError_t pdrnn_lstm_decode_beam_select(const float* logits, float* cum, int32_
   if (G < 1 || W < 1 || G > pdrnn::kStreams || W > pdrnn::kStreams || G * W > pdrnn::kStreams || V < 1 || V > 1024 ||
       stop < -1 || stop >= V)
     return hipErrorInvalidValue;
-  const pdrnn::BeamArgs b{logits, cum, done, tokens, parents, lp, G, W, V, 1, stop, 0};
+  const pdrnn::BeamArgs b{logits, cum, done, tokens, parents, lp, G, W, V, 1, stop};
   pdrnn::lstm_decode_beam_pick<<<1, pdrnn::kThreads, 0, stream>>>(b, 0, nullptr, nullptr);
   return hipGetLastError();
 }

@@ -14,6 +14,7 @@ MI355X), the loss in fp32.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional, Tuple
 
 import torch
@@ -67,6 +68,35 @@ class CharLM(nn.Module):
         logits = self.forward(tokens, carry=True)
         return logits[-1], self._state
 
+    @contextlib.contextmanager
+    def _decoding(self, what: str, prompt: Tensor, state, forced: Optional[Tensor] = None):
+        """What ``generate`` and ``beam_search`` do around their positions:
+        ``prompt`` [B, P] goes to the device (ValueError unless P >= 1, or where
+        it or ``forced``, on the CPU, hold tokens outside the vocabulary), the
+        model runs in eval mode and ``prompt[:, :-1]`` through ``_step`` from
+        ``state``; the training mode and the truncated-BPTT carry are put back
+        on the way out.  Yields (P, the first input tokens [B], the state after
+        the prefix, the compute dtype, whether the LSTM is one the decode
+        kernels know: biases, one direction, no projection)."""
+        if prompt.dim() != 2 or prompt.shape[1] < 1:
+            raise ValueError(f"{what}: prompt must be [B, P] with P >= 1")
+        dev = self.embedding.weight.device
+        prompt = prompt.to(dev, torch.int64)
+        for name, t in (("prompt", prompt), ("forced", forced)):
+            if t is not None and t.device.type == "cpu" and t.numel() and not (0 <= int(t.min()) and int(t.max()) < self.vocab_size):
+                raise ValueError(f"{what}: {name} holds tokens outside the vocabulary")
+        P = prompt.shape[1]
+        kept, training = self._state, self.training
+        self.eval()
+        try:
+            if P > 1:
+                _, state = self._step(prompt[:, :-1], state)
+            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+            yield P, prompt[:, -1], state, self._cdt(dev), plain
+        finally:
+            self._state = kept
+            self.train(training)
+
     @torch.no_grad()
     def generate(self, prompt: Tensor, num_tokens: int, temperature: float = 1.0, seed: int = 0,
                  state: Optional[Tuple[Tensor, Tensor]] = None, forced: Optional[Tensor] = None,
@@ -103,32 +133,19 @@ class CharLM(nn.Module):
         and the truncated-BPTT carry is left as it was."""
         from .. import _ext
         from ..ops import decode as dec
-        if prompt.dim() != 2 or prompt.shape[1] < 1:
-            raise ValueError("generate: prompt must be [B, P] with P >= 1")
         dev = self.embedding.weight.device
-        prompt = prompt.to(dev, torch.int64)
         forced = forced.to(dev, torch.int64) if forced is not None else None
-        B, P = prompt.shape
         N = int(num_tokens)
-        if forced is not None and tuple(forced.shape) != (B, N):
+        if forced is not None and prompt.dim() == 2 and tuple(forced.shape) != (prompt.shape[0], N):
             raise ValueError("generate: forced must be [B, num_tokens]")
         dec.check_filters(top_k, top_p)
         if stop is not None and forced is not None:
             raise ValueError("generate: stop and forced exclude each other")
         if stop is not None and not 0 <= int(stop) < self.vocab_size:
             raise ValueError(f"generate: stop token {stop} is outside the vocabulary")
-        for name, t in (("prompt", prompt), ("forced", forced)):
-            if t is not None and t.device.type == "cpu" and t.numel() and not (0 <= int(t.min()) and int(t.max()) < self.vocab_size):
-                raise ValueError(f"generate: {name} holds tokens outside the vocabulary")
         V, E, H, L = self.vocab_size, self.embedding.embedding_dim, self.hidden_dim, self.num_layers
-        kept, training = self._state, self.training
-        self.eval()
-        try:
-            if P > 1:
-                _, state = self._step(prompt[:, :-1], state)
-            first = prompt[:, -1]
-            cdt = self._cdt(dev)
-            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+        with self._decoding("generate", prompt, state, forced) as (P, first, state, cdt, plain):
+            B = first.shape[0]
             logprobs = None
             filt = dict(top_k=top_k, top_p=top_p, return_logprobs=return_logprobs)
             if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev):
@@ -158,18 +175,13 @@ class CharLM(nn.Module):
                 logprobs = rest[0] if return_logprobs else None
                 if return_logits and logits is None:  # (no position at all)
                     logits = torch.empty(B, 0, V, device=dev)
-        finally:
-            self._state = kept
-            self.train(training)
         lengths = None
         if stop is not None or return_lengths:
-            hit = tokens == stop if stop is not None else torch.zeros_like(tokens, dtype=torch.bool)
-            before = hit.cumsum(dim=1) - hit.to(torch.int64)  # a row's stop tokens before each position
-            lengths = ((before == 0).sum(dim=1)).to(torch.int64)  # up to and including the first
+            lengths, past = dec.stop_lengths(tokens, stop)
             if stop is not None:
-                tokens = torch.where(before > 0, torch.full_like(tokens, int(stop)), tokens)
+                tokens = torch.where(past, torch.full_like(tokens, int(stop)), tokens)
                 if logprobs is not None:
-                    logprobs = torch.where(before > 0, torch.zeros_like(logprobs), logprobs)
+                    logprobs = torch.where(past, torch.zeros_like(logprobs), logprobs)
         out = ((tokens,) + ((logits,) if return_logits else ()) + ((logprobs,) if return_logprobs else ())
                + ((lengths,) if return_lengths else ()) + ((state,) if return_state else ()))
         return out[0] if len(out) == 1 else out
@@ -203,24 +215,12 @@ class CharLM(nn.Module):
         carry is left as it was."""
         from .. import _ext
         from ..ops import decode as dec
-        if prompt.dim() != 2 or prompt.shape[1] < 1:
-            raise ValueError("beam_search: prompt must be [B, P] with P >= 1")
         V, E, H, L = self.vocab_size, self.embedding.embedding_dim, self.hidden_dim, self.num_layers
         dec.check_beam(beam_width, stop, V, num_tokens)
         dev = self.embedding.weight.device
-        prompt = prompt.to(dev, torch.int64)
-        if prompt.device.type == "cpu" and prompt.numel() and not (0 <= int(prompt.min()) and int(prompt.max()) < V):
-            raise ValueError("beam_search: prompt holds tokens outside the vocabulary")
-        B, P = prompt.shape
         N, W = int(num_tokens), int(beam_width)
-        kept, training = self._state, self.training
-        self.eval()
-        try:
-            if P > 1:
-                _, state = self._step(prompt[:, :-1], state)
-            first = prompt[:, -1]
-            cdt = self._cdt(dev)
-            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+        with self._decoding("beam_search", prompt, state) as (_, first, state, cdt, plain):
+            B = first.shape[0]
             per = dec.MAX_STREAMS // W
             if plain and dec.beam_supported(min(B, per), W, H, E, V, L, cdt, dev):
                 outs = []
@@ -237,9 +237,6 @@ class CharLM(nn.Module):
             hyp, scores = torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0).float()
             logprobs = torch.cat([o[2] for o in outs], 0).float() if return_logprobs else None
             h, c = torch.cat([o[3] for o in outs], 1), torch.cat([o[4] for o in outs], 1)
-        finally:
-            self._state = kept
-            self.train(training)
         order, lengths, scores = dec.beam_finish(hyp, scores, stop, length_penalty)
         if length_penalty:
             hyp = hyp.gather(1, order[:, :, None].expand_as(hyp))

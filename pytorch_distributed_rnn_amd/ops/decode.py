@@ -72,13 +72,10 @@ from . import shadow as _sh
 from .lstm_large import _DTYPE_CODE, _bias_cat, shadow
 
 __all__ = ["gumbel_noise", "keep_threshold", "token_logprobs", "check_filters", "sample", "supported", "alloc_buffers",
-           "decode", "reference", "MAX_STREAMS", "check_beam", "beam_start", "beam_select", "beam_backtrace", "beam_finish",
-           "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
+           "decode", "reference", "MAX_STREAMS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
+           "stop_lengths", "beam_finish", "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
 
 MAX_STREAMS = 16  # streams per launch: the 16-wide side of the MFMA tile
-# beam search: every selection a one-workgroup launch of its own instead of inside the layer-0 launch.
-# The same results; slower where measured (profiles/r15/beam.md), kept for that measurement.
-BEAM_SELECT_LAUNCH = False
 _M32 = 0xFFFFFFFF
 
 
@@ -200,17 +197,42 @@ def sample(logits: Tensor, temperature: float, seed: int, streams: Tensor, pos: 
     return first_argmax(y)
 
 
-def supported(B: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
-    """The fused decode kernels run this shape on ``device``."""
+def _covered(op: str, dtype: torch.dtype, device, *shape: int) -> bool:
+    """The extension on ``device`` has ``op``, and ``<op>_supported`` covers ``shape`` in ``dtype``."""
     device = torch.device(device)
-    if device.type != "cuda" or dtype not in _DTYPE_CODE:
-        return False
-    mod = _ext.native(device)
+    mod = _ext.native(device) if device.type == "cuda" and dtype in _DTYPE_CODE else None
     if mod is None:
         return False
-    if not hasattr(mod, "lstm_decode"):
-        raise RuntimeError("the native extension has no lstm_decode: rebuild it (python -m pytorch_distributed_rnn_amd._build)")
-    return bool(mod.lstm_decode_supported(B, H, E, V, L, _DTYPE_CODE[dtype]))
+    if not hasattr(mod, op):
+        raise RuntimeError(f"the native extension has no {op}: rebuild it (python -m pytorch_distributed_rnn_amd._build)")
+    return bool(getattr(mod, op + "_supported")(*shape, _DTYPE_CODE[dtype]))
+
+
+def supported(B: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
+    """The fused decode kernels run this shape on ``device``."""
+    return _covered("lstm_decode", dtype, device, B, H, E, V, L)
+
+
+def _stack_dims(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor) -> tuple:
+    """(the device, its extension or None, V, E, H, L) of a stack."""
+    return (emb_w.device, _ext.native(emb_w.device), *emb_w.shape, fc_w.shape[1], len(lstm_weights) // 4)
+
+
+def _stack_operands(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt) -> tuple:
+    """Both ops' leading arguments: emb, w_ih / w_hh / b_ih + b_hh per layer, fc_w, fc_b; the weights in
+    ``cdt`` from the shadow registry, the biases in fp32."""
+    H, L = fc_w.shape[1], len(lstm_weights) // 4
+    w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
+    w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
+    bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, emb_w.device) for l in range(L)]
+    return (_sh.cast(emb_w, cdt), w_ih, w_hh, bias, _sh.cast(fc_w, cdt), fc_b.detach().float() if fc_b is not None else None)
+
+
+def _alloc_stack(L: int, B: int, H: int, V: int, N: int, cdt, device, return_logits: bool) -> Dict[str, Optional[Tensor]]:
+    """What both ops work in: ``h``, ``c``, ``scratch`` and ``logits`` of ``alloc_buffers``."""
+    f32 = dict(device=device, dtype=torch.float32)
+    return {"h": torch.empty(2, L, B, H, device=device, dtype=cdt), "c": torch.empty(L, B, H, **f32),
+            "scratch": torch.empty(B, V, **f32), "logits": torch.empty(B, N, V, **f32) if return_logits else None}
 
 
 def alloc_buffers(L: int, B: int, H: int, V: int, N: int, cdt: torch.dtype, device,
@@ -222,9 +244,7 @@ def alloc_buffers(L: int, B: int, H: int, V: int, N: int, cdt: torch.dtype, devi
     ``logits`` [B, N, V], ``threshold`` [B, N], ``logprobs`` [B, N] fp32 or
     None."""
     f32 = dict(device=device, dtype=torch.float32)
-    return {"h": torch.empty(2, L, B, H, device=device, dtype=cdt), "c": torch.empty(L, B, H, **f32),
-            "scratch": torch.empty(B, V, **f32), "tokens": torch.empty(B, N, device=device, dtype=torch.int64),
-            "logits": torch.empty(B, N, V, **f32) if return_logits else None,
+    return {**_alloc_stack(L, B, H, V, N, cdt, device, return_logits), "tokens": torch.empty(B, N, device=device, dtype=torch.int64),
             "threshold": torch.empty(B, N, **f32) if return_threshold else None,
             "logprobs": torch.empty(B, N, **f32) if return_logprobs else None}
 
@@ -246,11 +266,7 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
     logits [B, N, V] or None, h [L, B, H] in ``cdt``, c [L, B, H] fp32), then
     the thresholds [B, N] and the tokens' log-probabilities [B, N] (fp32), each
     only when asked for: views of the buffers."""
-    dev = emb_w.device
-    mod = _ext.native(dev)
-    V, E = emb_w.shape
-    H = fc_w.shape[1]
-    L = len(lstm_weights) // 4
+    dev, mod, V, E, H, L = _stack_dims(emb_w, lstm_weights, fc_w)
     B, N = first.shape[0], int(num_tokens)
     if mod is None or not supported(B, H, E, V, L, cdt, dev):
         raise RuntimeError(f"lstm_decode does not cover B={B} H={H} E={E} V={V} L={L} {cdt} on {dev}")
@@ -258,17 +274,13 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
         raise ValueError("num_tokens must be at least 1")
     check_filters(top_k, top_p)
     with torch.no_grad():
-        w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
-        w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
-        bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, dev) for l in range(L)]
-        emb16, fc16 = _sh.cast(emb_w, cdt), _sh.cast(fc_w, cdt)
+        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt)
         if bufs is None:
             bufs = alloc_buffers(L, B, H, V, N, cdt, dev, return_logits, return_threshold, return_logprobs)
         h, c = bufs["h"], bufs["c"]
         h[0].copy_(h0) if h0 is not None else h[0].zero_()
         c.copy_(c0) if c0 is not None else c.zero_()
-        mod.lstm_decode(emb16, w_ih, w_hh, bias, fc16, fc_b.detach().float() if fc_b is not None else None, h, c,
-                        bufs["scratch"], first.to(dev, torch.int64).contiguous(),
+        mod.lstm_decode(*stack, h, c, bufs["scratch"], first.to(dev, torch.int64).contiguous(),
                         forced.to(dev, torch.int64).contiguous() if forced is not None else None, bufs["tokens"],
                         bufs["logits"] if return_logits else None, float(temperature), int(seed) & _M32,
                         int(stream0) & _M32, int(pos0) & _M32, top_k=min(int(top_k), V), top_p=float(top_p),
@@ -346,14 +358,20 @@ def beam_backtrace(tokens: Tensor, parents: Tensor, lp: Optional[Tensor] = None)
     return hyp, hyp_lp
 
 
+def stop_lengths(tokens: Tensor, stop: Optional[int]) -> Tuple[Tensor, Tensor]:
+    """tokens [..., N] -> (lengths [...] int64 up to and including the first ``stop``, N without one;
+    past [..., N] bool: the positions after it)."""
+    hit = tokens == stop if stop is not None else torch.zeros_like(tokens, dtype=torch.bool)
+    before = hit.cumsum(dim=-1) - hit.to(torch.int64)  # the stop tokens before each position
+    return (before == 0).sum(dim=-1).to(torch.int64), before > 0
+
+
 def beam_finish(hyp: Tensor, scores: Tensor, stop: Optional[int], length_penalty: float = 0.0):
     """Lengths and the final order, on the device with no host read: hyp
     [G, W, N], scores [G, W] in rank order -> (order [G, W], lengths [G, W]
     int64, ranked scores [G, W]).  A length counts up to and including the first
     ``stop``; ``length_penalty`` a != 0 re-ranks, stably, by score / length^a."""
-    hit = hyp == stop if stop is not None else torch.zeros_like(hyp, dtype=torch.bool)
-    before = hit.cumsum(dim=-1) - hit.to(torch.int64)
-    lengths = (before == 0).sum(dim=-1).to(torch.int64)
+    lengths, _ = stop_lengths(hyp, stop)
     order = torch.arange(hyp.shape[1], device=hyp.device).expand(hyp.shape[0], -1)
     if length_penalty:
         scores = scores / lengths.to(scores.dtype) ** float(length_penalty)
@@ -365,15 +383,7 @@ def beam_finish(hyp: Tensor, scores: Tensor, stop: Optional[int], length_penalty
 
 def beam_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
     """The fused decode kernels run a beam search of G groups of W beams."""
-    device = torch.device(device)
-    if device.type != "cuda" or dtype not in _DTYPE_CODE:
-        return False
-    mod = _ext.native(device)
-    if mod is None:
-        return False
-    if not hasattr(mod, "lstm_decode_beam"):
-        raise RuntimeError("the native extension has no lstm_decode_beam: rebuild it (python -m pytorch_distributed_rnn_amd._build)")
-    return bool(mod.lstm_decode_beam_supported(G, W, H, E, V, L, _DTYPE_CODE[dtype]))
+    return _covered("lstm_decode_beam", dtype, device, G, W, H, E, V, L)
 
 
 def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torch.dtype, device,
@@ -389,46 +399,34 @@ def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torc
     f32 = dict(device=device, dtype=torch.float32)
     i64 = dict(device=device, dtype=torch.int64)
     i32 = dict(device=device, dtype=torch.int32)
-    return {"h": torch.empty(2, L, S, H, device=device, dtype=cdt), "c": torch.empty(L, S, H, **f32),
-            "scratch": torch.empty(S, V, **f32), "cum": torch.empty(N + 1, S, **f32), "done": torch.empty(N + 1, S, **i32),
+    return {**_alloc_stack(L, S, H, V, N, cdt, device, return_logits),
+            "cum": torch.empty(N + 1, S, **f32), "done": torch.empty(N + 1, S, **i32),
             "tokens": torch.empty(S, N, **i64), "parents": torch.empty(S, N, **i32),
-            "lp": torch.empty(S, N, **f32) if return_logprobs else None,
-            "logits": torch.empty(S, N, V, **f32) if return_logits else None, "hyp": torch.empty(S, N, **i64),
+            "lp": torch.empty(S, N, **f32) if return_logprobs else None, "hyp": torch.empty(S, N, **i64),
             "hyp_lp": torch.empty(S, N, **f32) if return_logprobs else None}
 
 
 def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt: torch.dtype,
                 h0: Optional[Tensor], c0: Optional[Tensor], first: Tensor, num_tokens: int, width: int, *,
                 stop: Optional[int] = None, return_logits: bool = False, return_logprobs: bool = False,
-                bufs: Optional[Dict[str, Optional[Tensor]]] = None, select_launch: Optional[bool] = None):
+                bufs: Optional[Dict[str, Optional[Tensor]]] = None):
     """Beam search over ``num_tokens`` positions on the fused kernels: G =
     len(first) prompts, ``width`` beams each, G * width <= 16.
 
     The weights as in ``decode`` (16-bit copies from the shadow registry); h0 /
     c0 [L, G, H] or None: each prompt's state, which all its beams start from;
     first [G]: the prompts' last tokens.  ``bufs``: caller-made buffers
-    (``alloc_beam_buffers``); they keep every selection's record.
-    ``select_launch``: every selection in a launch of its own instead of inside
-    the layer-0 launch (the measured alternative; the same results; None:
-    ``BEAM_SELECT_LAUNCH``).  Returns
+    (``alloc_beam_buffers``); they keep every selection's record.  Returns
     (hyp [G, W, N] int64 in rank order, scores [G, W] fp32, hyp_lp [G, W, N] or
     None, h [L, G * W, H] in ``cdt``, c [L, G * W, H] fp32): the state entering
     position N of each hypothesis, the last token not fed, as in ``decode``."""
-    dev = emb_w.device
-    mod = _ext.native(dev)
-    V, E = emb_w.shape
-    H = fc_w.shape[1]
-    L = len(lstm_weights) // 4
+    dev, mod, V, E, H, L = _stack_dims(emb_w, lstm_weights, fc_w)
     G, N, W = first.shape[0], int(num_tokens), int(width)
     check_beam(width, stop, V, N, G)
     if mod is None or not beam_supported(G, W, H, E, V, L, cdt, dev):
         raise RuntimeError(f"lstm_decode_beam does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
-    S = G * W
     with torch.no_grad():
-        w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
-        w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
-        bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, dev) for l in range(L)]
-        emb16, fc16 = _sh.cast(emb_w, cdt), _sh.cast(fc_w, cdt)
+        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt)
         if bufs is None:
             bufs = alloc_beam_buffers(L, G, W, H, V, N, cdt, dev, return_logits, return_logprobs)
         h, c = bufs["h"], bufs["c"]
@@ -436,12 +434,11 @@ def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_
         c.view(L, G, W, H).copy_(c0[:, :, None, :]) if c0 is not None else c.zero_()
         bufs["cum"][0].copy_(beam_start(G, W, dev))
         bufs["done"][0].zero_()
-        mod.lstm_decode_beam(emb16, w_ih, w_hh, bias, fc16, fc_b.detach().float() if fc_b is not None else None, h, c,
-                             bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(), bufs["cum"],
-                             bufs["done"], bufs["tokens"], bufs["parents"], bufs["lp"] if return_logprobs else None,
-                             bufs["logits"] if return_logits else None, bufs["hyp"],
-                             bufs["hyp_lp"] if return_logprobs else None, G, W, -1 if stop is None else int(stop),
-                             BEAM_SELECT_LAUNCH if select_launch is None else bool(select_launch))
+        mod.lstm_decode_beam(*stack, h, c, bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(),
+                             bufs["cum"], bufs["done"], bufs["tokens"], bufs["parents"],
+                             bufs["lp"] if return_logprobs else None, bufs["logits"] if return_logits else None,
+                             bufs["hyp"], bufs["hyp_lp"] if return_logprobs else None, G, W,
+                             -1 if stop is None else int(stop))
         last = bufs["parents"][:, N - 1].to(torch.int64)
         hn, cn = h[N & 1].index_select(1, last), c.index_select(1, last)
     return (bufs["hyp"].view(G, W, N), bufs["cum"][N].view(G, W),

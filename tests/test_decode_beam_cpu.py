@@ -23,7 +23,7 @@ import _beam_ref as R
 
 F64 = torch.float64
 INF = float("inf")
-SELECT_V = [1, 8, 63, 64, 65, 256, 1000, 1024]
+SELECT_V = [1, 8, 63, 64, 65, 256, 300, 512, 1000, 1024]
 SELECT_GW = [(1, 1), (16, 1), (1, 16), (5, 3), (2, 8), (3, 5)]
 
 

@@ -22,7 +22,7 @@ from pytorch_distributed_rnn_amd.ops import decode as dec
 
 F64 = torch.float64
 INF = float("inf")
-VS = [1, 8, 24, 64, 65, 256, 1000, 1024]
+VS = [1, 8, 24, 64, 65, 256, 300, 512, 1000, 1024]
 DEFECTS = ("index_tie_break", "p_before_k", "no_renormalisation", "strict_compare")
 # 0.999 quantiles of chi-square
 CHI2_999 = {2: 13.816, 4: 18.467}

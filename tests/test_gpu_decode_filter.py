@@ -146,7 +146,7 @@ def _rows(V):
 
 
 @pytest.mark.parametrize("cdt", DTYPES, ids=["bf16", "fp16"])
-@pytest.mark.parametrize("V", [8, 24, 64, 65, 256, 1000, 1024])
+@pytest.mark.parametrize("V", [8, 24, 64, 65, 256, 300, 512, 1000, 1024])
 def test_top_k_threshold_is_exact(V, cdt):
     """threshold == the k-th largest of the kernels' own logits, bit for bit,
     at every position of every stream; -inf where top_k >= V.  All buffers
