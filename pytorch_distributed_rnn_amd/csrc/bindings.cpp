@@ -957,6 +957,7 @@ Tensor embedding_fwd(const Tensor& weight, const Tensor& idx, optional<at::Scala
   CHECK_HIP_TENSOR(weight); CHECK_F32(weight);
   TORCH_CHECK(weight.is_contiguous() && weight.dim() == 2);
   TORCH_CHECK(idx.scalar_type() == at::kLong);
+  TORCH_CHECK(idx.device() == weight.device(), "embedding_fwd: idx on ", idx.device(), ", weight on ", weight.device());
   const c10::DeviceGuard guard(weight.device());
   Tensor flat = idx.contiguous().view({-1});
   std::vector<int64_t> shape(idx.sizes().begin(), idx.sizes().end());
@@ -978,6 +979,12 @@ Tensor embedding_fwd(const Tensor& weight, const Tensor& idx, optional<at::Scala
 Tensor embedding_bwd(const Tensor& dout, const Tensor& idx, int64_t num_embeddings, int64_t padding_idx,
                      const optional<Tensor>& out) {
   CHECK_HIP_TENSOR(dout);
+  TORCH_CHECK(dout.dim() >= 1 && dout.size(-1) > 0, "embedding_bwd: dout [..., dim] with dim > 0");
+  TORCH_CHECK(idx.device() == dout.device(), "embedding_bwd: idx on ", idx.device(), ", dout on ", dout.device());
+  TORCH_CHECK(idx.numel() == dout.numel() / dout.size(-1), "embedding_bwd: ", idx.numel(), " indices for ",
+              dout.numel() / dout.size(-1), " rows of dout");
+  TORCH_CHECK(!(out.has_value() && out->defined()) || out->device() == dout.device(), "embedding_bwd: out on ",
+              out->device(), ", dout on ", dout.device());
   const c10::DeviceGuard guard(dout.device());
   const int64_t dim = dout.size(-1);
   Tensor g = dout.contiguous().view({-1, dim});

@@ -312,9 +312,6 @@ hipError_t pdrnn_embedding_bwd_pieces(const void* dout, int dout_dtype, const in
 hipError_t pdrnn_embedding_bwd_csr2(const void* dout, int dout_dtype, const int64_t* perm, const int64_t* offsets,
                                    float* dweight, int64_t num_embeddings, int64_t dim, int64_t padding_idx,
                                    hipStream_t stream);
-hipError_t pdrnn_embedding_bwd_csr(const float* dout, const int64_t* perm, const int64_t* offsets,
-                                   float* dweight, int64_t num_embeddings, int64_t dim,
-                                   int64_t padding_idx, hipStream_t stream);
 
 // ---- large-H LSTM (MFMA per-step kernels; bf16 / fp16 / fp32 storage) ------
 // Storage pointers are void*: elements of the dtype passed to the launchers

@@ -14,11 +14,10 @@ namespace {
 
 __global__ void __launch_bounds__(256) emb_fwd_kernel(const float* __restrict__ w, const int64_t* __restrict__ idx,
                                                       float* __restrict__ out, int64_t n, int64_t dim,
-                                                      int64_t V) {
+                                                      int64_t V, int vec) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const bool vec = (dim % 4) == 0;
   for (int64_t r = wave; r < n; r += nwaves) {
     int64_t v = idx[r];
     if (v < 0) v += V;
@@ -58,28 +57,7 @@ __global__ void __launch_bounds__(256) emb_fwd16_kernel(const float* __restrict_
 }
 
 // dweight[v] = sum over j in [off[v], off[v+1]) of dout[perm[j]]; padding row -> 0.
-__global__ void __launch_bounds__(256) emb_bwd_csr_kernel(const float* __restrict__ dout,
-                                                          const int64_t* __restrict__ perm,
-                                                          const int64_t* __restrict__ off,
-                                                          float* __restrict__ dw, int64_t V, int64_t dim,
-                                                          int64_t padding_idx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t v = wave; v < V; v += nwaves) {
-    const int64_t j0 = off[v], j1 = off[v + 1];
-    float* dst = dw + v * dim;
-    for (int64_t c = lane; c < dim; c += 64) {
-      float acc = 0.f;
-      if (v != padding_idx)
-        for (int64_t j = j0; j < j1; ++j) acc += dout[perm[j] * dim + c];
-      dst[c] = acc;
-    }
-  }
-}
-
-// Same contract, latency-hiding form: one wave per (vocab row, 64-column
-// slice); the contribution list is walked 8 rows at a time (8 independent
+// One wave per (vocab row, 64-column slice); the contribution list is walked 8 rows at a time (8 independent
 // index loads, then 8 independent row loads, summed in list order -- still
 // bitwise deterministic).  dout may be fp32 / bf16 / fp16 (DT 2 / 0 / 1).
 template <int DT>
@@ -271,8 +249,11 @@ extern "C" {
 hipError_t pdrnn_embedding_fwd(const float* weight, const int64_t* idx, float* out, int64_t n_idx, int64_t dim,
                                int64_t num_embeddings, hipStream_t stream) {
   if (n_idx <= 0) return hipSuccess;
+  // 16 B per lane only when every row starts 16-byte aligned on both sides (a
+  // weight inside the flat parameter buffer may start at any float)
+  const int vec = dim % 4 == 0 && (((uintptr_t)weight | (uintptr_t)out) & 15) == 0;
   hipLaunchKernelGGL(pdrnn::emb_fwd_kernel, dim3(pdrnn::blocks_for(n_idx)), dim3(256), 0, stream, weight, idx, out,
-                     n_idx, dim, num_embeddings);
+                     n_idx, dim, num_embeddings, vec);
   return hipGetLastError();
 }
 
@@ -357,13 +338,6 @@ hipError_t pdrnn_embedding_sort(const int64_t* idx, int64_t n, int64_t V, int* s
   }
   hipLaunchKernelGGL(pdrnn::emb_scatter_kernel, dim3(nb), dim3(pdrnn::kSortTile), lds_scatter, stream, idx, n,
                      (int)V, scratch, perm);
-  return hipGetLastError();
-}
-
-hipError_t pdrnn_embedding_bwd_csr(const float* dout, const int64_t* perm, const int64_t* offsets, float* dweight,
-                                   int64_t num_embeddings, int64_t dim, int64_t padding_idx, hipStream_t stream) {
-  hipLaunchKernelGGL(pdrnn::emb_bwd_csr_kernel, dim3(pdrnn::blocks_for(num_embeddings)), dim3(256), 0, stream, dout,
-                     perm, offsets, dweight, num_embeddings, dim, padding_idx);
   return hipGetLastError();
 }
 

@@ -20,18 +20,13 @@
 #include <hip/hip_runtime.h>
 
 #include "pdrnn/api.h"
+#include "pdrnn/common.h"
 
 namespace pdrnn {
 namespace {
 
 constexpr int PK_T = 64;        // tile edge
 constexpr int PK_THREADS = 256;
-
-__device__ __forceinline__ uint16_t pk_bf16(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // quiet NaN
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                  // round to nearest even
-}
 
 __global__ void __launch_bounds__(PK_THREADS) shadow_pack_kernel(PdrnnPackBatch b) {
   __shared__ float tile[PK_T][PK_T + 1];
@@ -79,7 +74,7 @@ __global__ void __launch_bounds__(PK_THREADS) shadow_pack_kernel(PdrnnPackBatch 
         uint16_t o[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          o[q] = p.dtype == 1 ? __builtin_bit_cast(uint16_t, (_Float16)v[q]) : pk_bf16(v[q]);
+          o[q] = p.dtype == 1 ? __builtin_bit_cast(uint16_t, (_Float16)v[q]) : f32_to_bf16(v[q]);
         *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.dst) + dof) =
             make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
       }
@@ -115,7 +110,7 @@ __global__ void __launch_bounds__(PK_THREADS) shadow_pack_kernel(PdrnnPackBatch 
     } else if (p.dtype == 1) {
       static_cast<uint16_t*>(p.dst)[o] = __builtin_bit_cast(uint16_t, (_Float16)v);
     } else {
-      static_cast<uint16_t*>(p.dst)[o] = pk_bf16(v);
+      static_cast<uint16_t*>(p.dst)[o] = f32_to_bf16(v);
     }
   }
 }

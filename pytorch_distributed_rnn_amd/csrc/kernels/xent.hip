@@ -131,14 +131,19 @@ __global__ void xent_bwd_kernel(const float* __restrict__ src, const float* grad
   const float scale = stats[1] != 0.f ? grad_out[0] / stats[1] : 0.f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float v = src[i] * scale;
+    const float s = src[i];
+    const float v = s * scale;
     if constexpr (OD == 2) {
       static_cast<float*>(dst)[i] = v;
     } else if constexpr (OD == 1) {
-      static_cast<uint16_t*>(dst)[i] = __builtin_bit_cast(uint16_t, (_Float16)v);
+      // the fused form is s * scale + (+0): an exact -0 product comes out as
+      // +0 -- give a zero of a zero operand the product's sign back
+      uint16_t h = __builtin_bit_cast(uint16_t, (_Float16)v);
+      if ((h & 0x7fffu) == 0 && (s == 0.f || scale == 0.f))
+        h = (uint16_t)(((__float_as_uint(s) ^ __float_as_uint(scale)) >> 16) & 0x8000u);
+      static_cast<uint16_t*>(dst)[i] = h;
     } else {
-      const uint32_t u = __float_as_uint(v);  // round to nearest even (finite inputs)
-      static_cast<uint16_t*>(dst)[i] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+      static_cast<uint16_t*>(dst)[i] = f32_to_bf16(v);  // round to nearest even, a NaN stays a NaN
     }
   }
 }

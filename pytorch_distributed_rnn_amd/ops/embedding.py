@@ -39,7 +39,13 @@ class _Embedding(torch.autograd.Function):
 
 def embedding(idx: Tensor, weight: Tensor, out_dtype: Optional[torch.dtype] = None,
               padding_idx: Optional[int] = None) -> Tensor:
-    """``F.embedding`` with the cast to ``out_dtype`` fused into the gather."""
+    """``F.embedding`` with the cast to ``out_dtype`` fused into the gather.
+    A negative ``padding_idx`` counts from the last row, as in ``F.embedding``."""
+    if padding_idx is not None:
+        V = weight.shape[0]
+        if not -V <= padding_idx < V:
+            raise ValueError(f"embedding: padding_idx {padding_idx} outside the {V} rows")
+        padding_idx = padding_idx + V if padding_idx < 0 else padding_idx
     mod = _ext.native(weight.device)
     if mod is not None and weight.dtype == torch.float32 and weight.is_cuda:
         return _Embedding.apply(weight, idx, out_dtype, padding_idx)

@@ -69,6 +69,11 @@ class Shadow:
             ms.append(m)
         return ms
 
+    def holds(self, masters: Sequence[Optional[Tensor]]) -> bool:
+        """Whether the entry's live masters are exactly these tensors."""
+        return len(masters) == len(self.masters) and all(
+            (m is None) if r is None else (r() is m) for r, m in zip(self.masters, masters))
+
 
 def _sig(ms: Sequence[Optional[Tensor]]):
     return tuple((tuple(m.shape), m.dtype, m.device) if m is not None else None for m in ms)
@@ -88,19 +93,33 @@ def get(anchor: Tensor, key, masters: Sequence[Optional[Tensor]], alloc: Callabl
 
     ``alloc()`` makes the output buffers once. ``build(*masters)`` returns the
     jobs that fill them. A stale lookup refreshes every stale shadow on the
-    device in one launch."""
+    device in one launch. An entry belongs to the very tensors it was made
+    for: a master replaced by another tensor (a re-assigned Parameter), of the
+    same shape or not, gets a new entry, whether or not the old tensor is
+    still alive somewhere."""
     cache = getattr(anchor, "_pdrnn_shadow", None)
     if cache is None:
         cache = {}
         anchor._pdrnn_shadow = cache
-    ent = cache.get(key)
-    if ent is None or ent.dead or ent.sig != _sig(masters):
+
+    def new():
         with torch.no_grad():
-            ent = Shadow(masters, build, alloc())
-        cache[key] = ent
-        _REG.setdefault(_dev_key(anchor.device), weakref.WeakSet()).add(ent)
-    if ent.ver != _version(masters):
+            e = Shadow(masters, build, alloc())
+        cache[key] = e
+        _REG.setdefault(_dev_key(anchor.device), weakref.WeakSet()).add(e)
+        return e
+
+    ent = cache.get(key)
+    if ent is None or ent.dead or ent.sig != _sig(masters) or not ent.holds(masters):
+        ent = new()
+    ver = _version(masters)
+    if ent.ver != ver:
         refresh(anchor.device)
+        if ent.dead or ent.ver != ver:  # not rebuilt with the rest: rebuild it alone, never return it stale
+            ent = new()
+            with torch.no_grad():
+                jobs = ent.build(*[m.detach() if m is not None else None for m in masters])
+            _run(jobs, [(ent, ver)], anchor.device)
     return ent.out
 
 
@@ -110,6 +129,7 @@ def refresh(device: torch.device) -> int:
     if not reg:
         return 0
     jobs: List[Job] = []
+    pending: List[Tuple[Shadow, tuple]] = []
     for ent in list(reg):
         if ent.dead:
             continue
@@ -123,12 +143,21 @@ def refresh(device: torch.device) -> int:
             continue
         with torch.no_grad():
             jobs.extend(ent.build(*[m.detach() if m is not None else None for m in ms]))
+        pending.append((ent, ver))
+    return _run(jobs, pending, device)
+
+
+def _run(jobs: List[Job], pending: List[Tuple["Shadow", tuple]], device: torch.device) -> int:
+    """Pack ``jobs``; only once that returned are the entries marked fresh, so
+    a pack that raises leaves them stale and the next lookup rebuilds them."""
+    launches = pack(jobs, device)
+    for ent, ver in pending:
         ent.ver = ver
     if not jobs:
         return 0
     _STATS["refreshes"] += 1
     _STATS["jobs"] += len(jobs)
-    _STATS["launches"] += pack(jobs, device)
+    _STATS["launches"] += launches
     return len(jobs)
 
 

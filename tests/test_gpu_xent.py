@@ -185,6 +185,26 @@ def test_xent_bwd_16bit_writers_round_to_nearest_even():
         _assert_rounded(got, g32, dtype)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32], ids=["bf16", "fp16", "fp32"])
+def test_xent_bwd_writers_on_special_values(dtype):
+    """Upstream gradient 1 and one valid row (scale exactly 1): every writer of
+    xent_bwd returns its source rounded once -- rounding ties both ways, the
+    edges of the 16-bit ranges, fp16 subnormals, signed zeros and infinities
+    bit for bit, and a NaN of any bit pattern (0x7fffffff and 0xffffffff, which
+    an unguarded ``u + 0x7fff`` turns into -0 and +0, and 0x7f800001) stays a
+    NaN.  The table holds no fp32 subnormal."""
+    import _embedding_ref as E
+    src = E.special_values()
+    b = E.special_bits()
+    for nan in (0x7fffffff, 0xffffffff, 0x7f800001):
+        assert torch.isnan(src[(b == nan).nonzero()[0, 0]])
+    src = src.repeat(5).view(5, -1)   # more than one block of 256
+    stats = torch.tensor([0.0, 1.0, 0.0], device="cuda")
+    got = _mod().xent_bwd(src.cuda(), torch.ones(1, device="cuda"), stats, dtype)
+    assert got.dtype == dtype and got.shape == src.shape
+    E.assert_bits(got, src.to(dtype), str(dtype))
+
+
 def test_xent_argmax_ties_take_the_first_index():
     """The maximum at two columns: the lower column is the prediction --
     columns 3 and 67 meet in one lane's strided loop, 3 and 10 in the wave

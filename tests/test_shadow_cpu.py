@@ -90,6 +90,106 @@ def test_registry_keeps_no_parameter_alive():
     assert sh.refresh(torch.device("cpu")) == 0
 
 
+def _lstm_weights(H, I, seed):
+    g = torch.Generator().manual_seed(seed)
+    return [torch.nn.Parameter(torch.randn(4 * H, I, generator=g)), torch.nn.Parameter(torch.randn(4 * H, H, generator=g)),
+            torch.nn.Parameter(torch.randn(4 * H, generator=g)), torch.nn.Parameter(torch.randn(4 * H, generator=g))]
+
+
+def _bias_ref(w, H):
+    return _interleaved((w[2] + w[3]).detach().view(4 * H, 1), H).view(-1)
+
+
+def test_replaced_bias_while_the_old_one_is_alive():
+    """A new Parameter of the same shape assigned over b_hh while something
+    (an optimizer) still holds the old one: the key carries no tensor ids, so
+    the entry must notice that its masters are not the tensors passed.  The
+    first lookup is right and costs exactly one refresh; later ones none."""
+    H = 4
+    w = _lstm_weights(H, 3, 0)
+    assert torch.equal(_bias_cat(w, 1, H, w[0].device), _bias_ref(w, H))
+    old = w[3]
+    w[3] = torch.nn.Parameter(old.detach() + 1.0)
+    before = sh.stats()["refreshes"]
+    assert torch.equal(_bias_cat(w, 1, H, w[0].device), _bias_ref(w, H))
+    assert sh.stats()["refreshes"] == before + 1
+    assert torch.equal(_bias_cat(w, 1, H, w[0].device), _bias_ref(w, H))
+    assert sh.stats()["refreshes"] == before + 1
+    assert old is not None  # kept alive to here
+
+
+def test_replaced_bias_after_the_old_one_is_freed():
+    """The same with the old Parameter gone: the first lookup after the change
+    must not return the stale buffer."""
+    H = 4
+    w = _lstm_weights(H, 3, 1)
+    assert torch.equal(_bias_cat(w, 1, H, w[0].device), _bias_ref(w, H))
+    ref = weakref.ref(w[3])
+    w[3] = torch.nn.Parameter(w[3].detach() + 1.0)
+    gc.collect()
+    assert ref() is None
+    before = sh.stats()["refreshes"]
+    assert torch.equal(_bias_cat(w, 1, H, w[0].device), _bias_ref(w, H))
+    assert sh.stats()["refreshes"] == before + 1
+
+
+def test_replaced_parameter_through_gru_shadows():
+    H, I = 4, 3
+    g = torch.Generator().manual_seed(2)
+    ws = [torch.nn.Parameter(torch.randn(3 * H, I, generator=g)), torch.nn.Parameter(torch.randn(3 * H, H, generator=g)),
+          torch.nn.Parameter(torch.randn(3 * H, generator=g)), torch.nn.Parameter(torch.randn(3 * H, generator=g))]
+
+    def bias_ref():
+        b_ih, b_hh = ws[2].detach(), ws[3].detach()
+        bias = torch.cat([b_ih[:2 * H] + b_hh[:2 * H], b_ih[2 * H:], b_hh[2 * H:]])
+        return _interleaved(bias.view(-1, 1), H).view(-1)
+
+    assert torch.equal(_gru_shadows(ws, 1, H, I, torch.float32, "cpu")[5], bias_ref())
+    for keep_old in (True, False):
+        old = ws[3]
+        ws[3] = torch.nn.Parameter(old.detach() * 2.0 + 1.0)
+        if not keep_old:
+            del old
+            gc.collect()
+        before = sh.stats()["refreshes"]
+        out = _gru_shadows(ws, 1, H, I, torch.float32, "cpu")
+        assert torch.equal(out[5], bias_ref()), keep_old
+        assert torch.equal(out[2][0], torch.cat([ws[1][:2 * H], torch.zeros(H, H), ws[1][2 * H:]]).detach())
+        assert sh.stats()["refreshes"] == before + 1, keep_old
+    # and a replaced recurrent weight
+    ws[1] = torch.nn.Parameter(ws[1].detach() + 0.5)
+    out = _gru_shadows(ws, 1, H, I, torch.float32, "cpu")
+    assert torch.equal(out[2][0], torch.cat([ws[1][:2 * H], torch.zeros(H, H), ws[1][2 * H:]]).detach())
+
+
+def test_pack_that_raises_leaves_the_shadows_stale(monkeypatch):
+    """refresh() marks an entry fresh only after pack() returned: a pack that
+    raises once (a launch error) must not leave pre-update weights cached as
+    current."""
+    H = 4
+    w = _lstm_weights(H, 3, 3)
+    dt = torch.bfloat16
+    assert torch.equal(shadow(w[1], "t", dt, H), w[1].detach().t().to(dt))
+    with torch.no_grad():
+        w[1].add_(0.5)
+    real, calls = sh.pack, []
+
+    def failing(jobs, device=None):
+        calls.append(len(jobs))
+        raise RuntimeError("pack failed")
+
+    monkeypatch.setattr(sh, "pack", failing)
+    try:
+        shadow(w[1], "t", dt, H)
+    except RuntimeError:
+        pass
+    else:
+        raise AssertionError("the failing pack was not reached")
+    monkeypatch.setattr(sh, "pack", real)
+    assert calls
+    assert torch.equal(shadow(w[1], "t", dt, H), w[1].detach().t().to(dt))
+
+
 def test_job_orders_unit_stride_dims_into_the_tile():
     a = torch.empty(6, 4, 64)   # dst [H, 4, k]
     src = torch.empty(4, 6, 64).transpose(0, 1)
