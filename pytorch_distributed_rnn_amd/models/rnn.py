@@ -19,6 +19,17 @@ from ..ops import gru as gru_ops
 from ..ops import lstm as lstm_ops
 
 
+def _stack_weights(self):
+    """The forward direction's (w_ih, w_hh, b_ih, b_hh) per layer; None for an absent bias."""
+    ws = []
+    for l in range(self.num_layers):
+        sfx = f"_l{l}"
+        ws += [getattr(self, "weight_ih" + sfx), getattr(self, "weight_hh" + sfx),
+               getattr(self, "bias_ih" + sfx) if self.bias else None,
+               getattr(self, "bias_hh" + sfx) if self.bias else None]
+    return ws
+
+
 class LSTM(nn.LSTM):
     """``nn.LSTM`` whose forward runs on the fused MI355X kernels.
 
@@ -26,14 +37,7 @@ class LSTM(nn.LSTM):
     ``h_n`` (e.g. a last-timestep classifier) skip the per-timestep output
     stream at inference."""
 
-    def _weights(self):
-        ws = []
-        for l in range(self.num_layers):
-            sfx = f"_l{l}"
-            ws += [getattr(self, "weight_ih" + sfx), getattr(self, "weight_hh" + sfx),
-                   getattr(self, "bias_ih" + sfx) if self.bias else None,
-                   getattr(self, "bias_hh" + sfx) if self.bias else None]
-        return ws
+    _weights = _stack_weights
 
     def forward(self, input, hx: Optional[Tuple[Tensor, Tensor]] = None, *, need_out: bool = True,
                 idx: Optional[Tensor] = None):  # type: ignore[override]
@@ -68,14 +72,7 @@ class GRU(nn.GRU):
     """``nn.GRU`` whose forward runs on the fused MI355X GRU kernels (small H,
     fp32) or the MFMA step kernels (16-bit, H % 64 == 0, also bidirectional)."""
 
-    def _weights(self):
-        ws = []
-        for l in range(self.num_layers):
-            sfx = f"_l{l}"
-            ws += [getattr(self, "weight_ih" + sfx), getattr(self, "weight_hh" + sfx),
-                   getattr(self, "bias_ih" + sfx) if self.bias else None,
-                   getattr(self, "bias_hh" + sfx) if self.bias else None]
-        return ws
+    _weights = _stack_weights
 
     def forward(self, input, hx: Optional[Tensor] = None):  # type: ignore[override]
         if isinstance(input, nn.utils.rnn.PackedSequence):

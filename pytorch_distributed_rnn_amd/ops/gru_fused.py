@@ -21,19 +21,6 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from .. import _ext
-
-
-def supported(x: Tensor, hidden: int, num_layers: int) -> bool:
-    if x.dtype != torch.float32 or x.dim() != 3 or x.device.type != "cuda":
-        return False
-    mod = _ext.native(x.device)
-    if mod is None or not mod.lstm_small_supported(hidden, x.shape[-1], num_layers):
-        return False
-    lanes = 8 if hidden >= 64 else 4
-    return num_layers * 4 * hidden <= 512 and num_layers * hidden * lanes <= 512
-
-
 _ZEROS: Dict[Tuple[torch.device, torch.dtype], Tensor] = {}
 # superseded zero vectors stay referenced: a cat on another stream may still
 # be reading one (they are never written, so sharing is safe; a few KB each)
@@ -112,48 +99,33 @@ def _unpack_index(hidden: int, in_dims: Tuple[int, ...], device: torch.device) -
     return idx
 
 
-class _FusedSmallGRU(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, h0, cfg, *weights):
-        hidden, num_layers, batch_first = cfg
-        mod = _ext.native(x.device)
-        packed = _pack(weights, num_layers, hidden, x)
-        h0c = h0.contiguous() if h0 is not None else None
-        out, hn, _, act = mod.lstm_small_fwd(x, None, packed, h0c, None, hidden, num_layers, batch_first,
-                                             True, True, 1, 1, cell=1)
-        ctx.set_materialize_grads(False)
-        ctx.cfg = (hidden, num_layers, batch_first, [w is not None for w in weights])
-        ctx.save_for_backward(x, h0c, out, act, *packed)
-        top = out[num_layers - 1]
-        if not batch_first:
-            top = top.transpose(0, 1)
-        return top, hn
-
-    @staticmethod
-    def backward(ctx, dout, dhn):
-        x, h0, hseq, act, *packed = ctx.saved_tensors
-        hidden, num_layers, batch_first, present = ctx.cfg
-        H = hidden
-        mod = _ext.native(x.device)
-        need_dx = ctx.needs_input_grad[0]
-        need_dh0 = ctx.needs_input_grad[1]
-        if dout is not None and dout.stride(-1) != 1:
-            dout = dout.contiguous()
-        dhn = dhn.contiguous() if dhn is not None else None
-        dparams, dx, dh0, _ = mod.lstm_small_bwd(x, None, packed, h0, None, hseq, act, dout, dhn, None, H,
-                                                 num_layers, batch_first, need_dx, need_dh0, 1, 1, None, cell=1)
-        in_dims = tuple(int(packed[4 * l].shape[1]) for l in range(num_layers))
-        g = dparams.index_select(0, _unpack_index(H, in_dims, dparams.device))
-        grads: List[Optional[Tensor]] = []
-        off = 0
-        for l, I in enumerate(in_dims):
-            for k, s in enumerate(((3 * H, I), (3 * H, H), (3 * H,), (3 * H,))):
-                n = s[0] * (s[1] if len(s) > 1 else 1)
-                grads.append(g[off:off + n].view(s) if present[4 * l + k] else None)
-                off += n
-        return (dx if need_dx else None, dh0 if need_dh0 else None, None, *grads)
+def _unpack(dparams: Tensor, packed: Sequence[Tensor], present: Sequence[bool],
+            hidden: int) -> List[Optional[Tensor]]:
+    """The packed gradient vector as nn.GRU's parameter gradients (None for
+    a bias the module does not have)."""
+    H = hidden
+    in_dims = tuple(int(w.shape[1]) for w in packed[::4])
+    g = dparams.index_select(0, _unpack_index(H, in_dims, dparams.device))
+    grads: List[Optional[Tensor]] = []
+    off = 0
+    for l, I in enumerate(in_dims):
+        for k, s in enumerate(((3 * H, I), (3 * H, H), (3 * H,), (3 * H,))):
+            n = s[0] * (s[1] if len(s) > 1 else 1)
+            grads.append(g[off:off + n].view(s) if present[4 * l + k] else None)
+            off += n
+    return grads
 
 
-def fused_gru(x: Tensor, weights: Sequence[Optional[Tensor]], h0: Optional[Tensor], *, hidden: int,
-              num_layers: int, batch_first: bool) -> Tuple[Tensor, Tensor]:
-    return _FusedSmallGRU.apply(x, h0, (hidden, num_layers, batch_first), *weights)
+class PackBuffer:
+    """The packed stack in a persistent buffer, re-packed from the current
+    parameters on every call by one cat launch: no allocation after the first,
+    so a captured step re-packs on every replay."""
+
+    def __init__(self):
+        self.buf: Optional[Tensor] = None
+
+    def pack(self, weights: Sequence[Tensor], num_layers: int, hidden: int) -> List[Tensor]:
+        if self.buf is None:
+            self.buf = torch.empty(packed_numel(weights, num_layers, hidden), dtype=weights[0].dtype,
+                                   device=weights[0].device)
+        return _pack(weights, num_layers, hidden, weights[0], out=self.buf)

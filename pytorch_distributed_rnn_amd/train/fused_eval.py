@@ -26,6 +26,7 @@ from torch import Tensor, nn
 
 from .. import _ext
 from ..ops.gemm import col_sum
+from ..ops.gru_fused import PackBuffer
 
 
 def _inner(model: nn.Module) -> nn.Module:
@@ -100,7 +101,7 @@ class MotionEvalStep:
         self.bf16 = getattr(m, "compute_dtype", torch.float32) == torch.bfloat16
         self.acc = None  # [sum of batch mean losses, examples, correct], made by the first labelled batch
         self.batches = 0
-        self._gru_buf = None  # GRU: persistent [r|z|n_x|n_h] packing buffer
+        self._gru_pack = PackBuffer()  # GRU: persistent [r|z|n_x|n_h] packing buffer
 
     @property
     def m(self) -> nn.Module:
@@ -131,10 +132,7 @@ class MotionEvalStep:
             features = features.float()
         if not self.gru:
             return ws, features, 0
-        from ..ops.gru_fused import _pack, packed_numel
-        if self._gru_buf is None:
-            self._gru_buf = torch.empty(packed_numel(ws, self.NL, self.H), dtype=torch.float32, device=ws[0].device)
-        return _pack(ws, self.NL, self.H, ws[0], out=self._gru_buf), features, 1
+        return self._gru_pack.pack(ws, self.NL, self.H), features, 1
 
     @torch.no_grad()
     def __call__(self, features: Tensor, labels: Optional[Tensor] = None,

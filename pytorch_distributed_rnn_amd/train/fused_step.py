@@ -29,6 +29,8 @@ import torch
 from torch import Tensor, nn
 
 from .. import _ext
+from ..ops.gru_fused import PackBuffer, _unpack_index
+from ..ops.lstm import CELLS, step_launch_config
 from ..utils.flat import contiguous_span
 from ..utils.tracing import trace_range
 
@@ -58,10 +60,8 @@ def supported(model: nn.Module, optimizer, device: torch.device) -> bool:
     if mod.lstm_small_max_split(lstm.hidden_size, lstm.num_layers, False) != 1 or \
             mod.lstm_small_max_split(lstm.hidden_size, lstm.num_layers, True) != 1:
         return False
-    if m.cell == "gru":
-        H, NL = lstm.hidden_size, lstm.num_layers
-        if NL * 4 * H > 512 or NL * H * (8 if H >= 64 else 4) > 512:
-            return False
+    if not CELLS[m.cell].launch_ok(lstm.hidden_size, lstm.num_layers):
+        return False
     params = list(m.parameters())
     if any(p.dtype != torch.float32 for p in params):
         return False
@@ -109,7 +109,8 @@ class MotionTrainStep:
         # GRU: the kernels run nn.GRU's parameters packed as [r | z | n_x | n_h]
         # 4-block stacks (ops/gru_fused.py); the reduction writes gradients
         # back in nn.GRU order through a column map
-        self.gru = getattr(self.m, "cell", "lstm") == "gru"
+        self.cell = CELLS[getattr(self.m, "cell", "lstm")]
+        self.gru = self.cell.name == "gru"
         self.weights = []
         for l in range(self.NL):
             self.weights += [getattr(lstm, f"weight_ih_l{l}"), getattr(lstm, f"weight_hh_l{l}"),
@@ -128,7 +129,6 @@ class MotionTrainStep:
         self.bf16 = getattr(self.m, "compute_dtype", torch.float32) == torch.bfloat16
         self.colmap = None
         if self.gru:
-            from ..ops.gru_fused import _unpack_index
             in_dims = tuple(int(self.weights[4 * l].shape[1]) for l in range(self.NL))
             self.colmap = _unpack_index(self.H, in_dims, self.flat.grad.device).to(torch.int32)
         base = self.flat.data.data_ptr()
@@ -156,7 +156,7 @@ class MotionTrainStep:
         self.cuda_graph = bool(cuda_graph)
         self._graph = None       # last replayed synced step (torch.cuda.CUDAGraph = hipGraph)
         self._graphs = {}        # configuration key -> captured step
-        self._gru_buf = None     # GRU: persistent [r|z|n_x|n_h] packing buffer (graph-capturable)
+        self._gru_pack = PackBuffer()  # GRU: persistent [r|z|n_x|n_h] packing buffer (graph-capturable)
 
     def _operands(self, features: Tensor):
         """(weights as the kernels read them, features, cell code): the bf16
@@ -169,12 +169,26 @@ class MotionTrainStep:
                 features = features.to(torch.bfloat16)
             return self.weights, features, 0
         if self.gru:
-            from ..ops.gru_fused import _pack, packed_numel
-            if self._gru_buf is None:
-                self._gru_buf = torch.empty(packed_numel(self.weights, self.NL, self.H), dtype=self.flat.data.dtype,
-                                            device=self.flat.data.device)
-            return _pack(self.weights, self.NL, self.H, self.flat.data, out=self._gru_buf), features, 1
+            return self._gru_pack.pack(self.weights, self.NL, self.H), features, 1
         return self.weights, features, 0
+
+    def _launch(self, features: Tensor, idx: Optional[Tensor], labels: Tensor, stats: Tensor, cfg,
+                adam_state=None, adam_hp=None, step: Optional[Tensor] = None, slot_off: int = 0,
+                ticket: Optional[Tensor] = None) -> None:
+        """Forward + head + CE, BPTT and the gradient reduction into the flat
+        buffer at launch config ``cfg`` (step_launch_config); with
+        ``adam_state`` / ``adam_hp`` Adam is folded into the reduction.
+        ``stats``: the row to write, or (captured steps) the whole ring with
+        row = device step count ``step`` + ``slot_off``; ``ticket``: the
+        folded Adam's arrival counter, which advances ``step``."""
+        (nb_fwd, split_fwd), nb_bwd = cfg
+        ws, features, cell = self._operands(features)
+        self.mod.lstm_head_train_step(
+            features, idx, labels, ws, head_w=self.m.fc.weight, head_b=self.m.fc.bias,  # (the head stays fp32)
+            flat_grad=self.flat.grad, stats=stats, H=self.H, NL=self.NL, split_fwd=split_fwd, split_bwd=0,
+            nb_fwd=nb_fwd, nb_bwd=nb_bwd, adam_state=adam_state, adam_hp=adam_hp, cell=cell,
+            grad_colmap=self.colmap, stats_slot_step=step, stats_slot_offset=slot_off, round_bf16=self.bf16,
+            adam_ticket=ticket)
 
     def run_steps(self, features: Tensor, labels: Tensor, idx_list) -> Optional[list]:
         """Consecutive training steps (an epoch's batches, the short last one
@@ -258,15 +272,8 @@ class MotionTrainStep:
         return [self.ring[slot] for slot in slots]
 
     def _epoch_key(self, features: Tensor, labels: Tensor, sizes, idx_dtype, adam):
-        from ..ops.lstm import fused_bwd_nb, small_launch_config
         (p, m, v), (lr, b1, b2, eps, wd, step, dec) = adam
-        cfgs = []
-        for b in sizes:
-            nb_fwd, sp_fwd, _, _ = small_launch_config(b, self.H, self.NL)
-            if self.gru:
-                from ..ops.lstm import gru_fwd_nb
-                nb_fwd, sp_fwd = gru_fwd_nb(b, self.H, features.device), 1
-            cfgs.append(((nb_fwd, sp_fwd), fused_bwd_nb(b, self.H, self.NL)))
+        cfgs = [step_launch_config(self.cell, b, self.H, self.NL, features.device) for b in sizes]
         key = ("epoch", features.data_ptr(), tuple(features.shape), features.dtype, labels.data_ptr(),
                labels.numel(), tuple(sizes), idx_dtype, tuple(cfgs), lr, b1, b2, eps, wd, dec,
                p.data_ptr(), m.data_ptr(), v.data_ptr(), self.flat.grad.data_ptr())
@@ -310,7 +317,6 @@ class MotionTrainStep:
     def _capture_epoch(self, ent: dict, features: Tensor, labels: Tensor, idx_list, cfgs, adam, slot: int):
         (p, m, v), (lr, b1, b2, eps, wd, step, dec) = adam
         dev = self.flat.grad.device
-        hw, hb = self.m.fc.weight, self.m.fc.bias
         sizes = [int(i.numel()) for i in idx_list]
         ent["idx_all"] = torch.cat(list(idx_list)).clone()
         offs = [sum(sizes[:k]) for k in range(len(sizes))]
@@ -324,21 +330,15 @@ class MotionTrainStep:
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            for view, ((nb, sp), nb_bwd) in zip(views, cfgs):
-                ws, feats, cell = self._operands(features)  # GRU: re-packed from the updated parameters
+            for view, cfg in zip(views, cfgs):  # (GRU: each step re-packs the updated parameters)
                 if self.grad_sync is None:
                     # one process: Adam folded into the reduction, which
                     # advances the device step count (the hyper-parameters'
                     # step slot is unused)
-                    self.mod.lstm_head_train_step(feats, view, labels, ws, hw, hb, self.flat.grad, self.ring,
-                                                  self.H, self.NL, sp, 0, nb, nb_bwd, [p, m, v],
-                                                  [lr, b1, b2, eps, wd, 1.0, dec], cell, self.colmap,
-                                                  ent["step"], ent["slot_off"], round_bf16=self.bf16,
-                                                  adam_ticket=ent["ticket"])
+                    self._launch(features, view, labels, self.ring, cfg, [p, m, v], [lr, b1, b2, eps, wd, 1.0, dec],
+                                 step=ent["step"], slot_off=ent["slot_off"], ticket=ent["ticket"])
                     continue
-                self.mod.lstm_head_train_step(feats, view, labels, ws, hw, hb, self.flat.grad, self.ring,
-                                              self.H, self.NL, sp, 0, nb, nb_bwd, None, None, cell, self.colmap,
-                                              ent["step"], ent["slot_off"], round_bf16=self.bf16)
+                self._launch(features, view, labels, self.ring, cfg, step=ent["step"], slot_off=ent["slot_off"])
                 self.grad_sync()
                 self.mod.adam_flat(p, self.flat.grad, m, v, None, lr, b1, b2, eps, wd, step + 1.0, 1.0, bool(dec),
                                    False, None, ent["step"], ent["ticket"])
@@ -375,32 +375,22 @@ class MotionTrainStep:
         return [fs["flat_p"], fs["exp_avg"], fs["exp_avg_sq"]], hp
 
     def __call__(self, features: Tensor, labels: Tensor, idx: Optional[Tensor]) -> Tensor:
-        from ..ops.lstm import fused_bwd_nb, gru_fwd_nb, small_launch_config
         self.flat.attach_grads()
-        batch = idx.numel() if idx is not None else features.shape[0]
-        nb_fwd, sp_fwd, _, _ = small_launch_config(batch, self.H, self.NL)
-        nb_bwd = fused_bwd_nb(batch, self.H, self.NL)
-        if self.gru:  # (gate-split family geometry; the sequence-in-wave kernels, H = 32, ignore it)
-            nb_fwd, sp_fwd = gru_fwd_nb(batch, self.H, features.device), 1
-        hw, hb = self.m.fc.weight, self.m.fc.bias  # the classifier head stays fp32
+        cfg = step_launch_config(self.cell, idx.numel() if idx is not None else features.shape[0], self.H, self.NL,
+                                 features.device)
         slot = self._slot
         stats = self.ring[slot]
         self._slot = (self._slot + 1) % self.RING
         adam = self._flat_adam()
         if self.grad_sync is not None and adam is not None and self.cuda_graph:
-            if self._graph_step(features, labels, idx, (nb_fwd, sp_fwd), nb_bwd, adam, stats, slot):
+            if self._graph_step(features, labels, idx, cfg, adam, stats, slot):
                 return stats
-        ws, features, cell = self._operands(features)
         if adam is not None and self.grad_sync is None:
             with trace_range("pdrnn.fwd_bwd_adam"):
-                self.mod.lstm_head_train_step(features, idx, labels, ws, hw, hb, self.flat.grad, stats, self.H,
-                                              self.NL, sp_fwd, 0, nb_fwd, nb_bwd, adam[0], adam[1], cell, self.colmap,
-                                              round_bf16=self.bf16)
+                self._launch(features, idx, labels, stats, cfg, adam[0], adam[1])
             return stats
         with trace_range("pdrnn.fwd_bwd"):
-            self.mod.lstm_head_train_step(
-                features, idx, labels, ws, hw, hb, self.flat.grad, stats, self.H, self.NL, sp_fwd, 0, nb_fwd, nb_bwd,
-                None, None, cell, self.colmap, round_bf16=self.bf16)
+            self._launch(features, idx, labels, stats, cfg)
         if self.grad_sync is not None:
             with trace_range("pdrnn.grad_allreduce"):
                 self.grad_sync()
@@ -418,14 +408,9 @@ class MotionTrainStep:
         discarded: loads the kernels' code objects and sizes the allocator's
         workspace for this batch shape.  Parameters and optimizer state are not
         touched; the flat gradient (fully rewritten by every step) is zeroed."""
-        from ..ops.lstm import fused_bwd_nb, gru_fwd_nb, small_launch_config
         self.flat.attach_grads()
-        batch = idx.numel() if idx is not None else features.shape[0]
-        nb_fwd, sp_fwd, _, _ = small_launch_config(batch, self.H, self.NL)
-        nb_bwd = fused_bwd_nb(batch, self.H, self.NL)
-        if self.gru:  # (gate-split family geometry; the sequence-in-wave kernels, H = 32, ignore it)
-            nb_fwd, sp_fwd = gru_fwd_nb(batch, self.H, features.device), 1
-        ws, features, cell = self._operands(features)
+        cfg = step_launch_config(self.cell, idx.numel() if idx is not None else features.shape[0], self.H, self.NL,
+                                 features.device)
         stats = torch.zeros(3, dtype=torch.float32, device=self.flat.grad.device)
         # the single-process step folds Adam into its reduction: warm THAT
         # kernel variant too (its first launch pays the code-object load), on
@@ -436,9 +421,7 @@ class MotionTrainStep:
             if st is not None:
                 (p, m, v), adam_hp = st
                 adam_bufs = [p.clone(), m.clone(), v.clone()]
-        self.mod.lstm_head_train_step(features, idx, labels, ws, self.m.fc.weight, self.m.fc.bias, self.flat.grad,
-                                      stats, self.H, self.NL, sp_fwd, 0, nb_fwd, nb_bwd, adam_bufs, adam_hp,
-                                      cell, self.colmap, round_bf16=self.bf16)
+        self._launch(features, idx, labels, stats, cfg, adam_bufs, adam_hp)
         self.flat.grad.zero_()
 
     def _flat_adam_peek(self):
@@ -458,8 +441,8 @@ class MotionTrainStep:
     # an epoch alternate: no re-capture every epoch)
     _GRAPHS_MAX = 4
 
-    def _graph_step(self, features: Tensor, labels: Tensor, idx: Optional[Tensor], nb_fwd,
-                    nb_bwd: int, adam, stats: Tensor, slot: int) -> bool:
+    def _graph_step(self, features: Tensor, labels: Tensor, idx: Optional[Tensor], cfg, adam, stats: Tensor,
+                    slot: int) -> bool:
         """Run the synced step as a graph replay.  False: run it eagerly --
         the first two steps of a configuration, so that RCCL's lazy connection
         setup and the kernels' first-use allocations happen outside the
@@ -468,7 +451,7 @@ class MotionTrainStep:
             return False  # host-gathered batches change pointers every step
         (p, m, v), (lr, b1, b2, eps, wd, step, dec) = adam
         key = (features.data_ptr(), tuple(features.shape), features.dtype, labels.data_ptr(), labels.numel(),
-               (idx.numel(), idx.dtype), nb_fwd, nb_bwd, lr, b1, b2, eps, wd, dec,
+               (idx.numel(), idx.dtype), *cfg, lr, b1, b2, eps, wd, dec,
                p.data_ptr(), m.data_ptr(), v.data_ptr(), self.flat.grad.data_ptr())
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.get(key)
@@ -482,7 +465,7 @@ class MotionTrainStep:
             if ent["eager"] <= 2:
                 return False
             try:
-                self._capture(ent, features, labels, idx, nb_fwd, nb_bwd, adam, slot)
+                self._capture(ent, features, labels, idx, cfg, adam, slot)
             except Exception as exc:  # capture unsupported here: stay eager for good
                 import warnings
                 warnings.warn(f"HIP graph capture of the synced step failed ({exc!r}); running eagerly")
@@ -509,11 +492,9 @@ class MotionTrainStep:
             stats.copy_(self.ring[row], non_blocking=True)
         return True
 
-    def _capture(self, ent: dict, features: Tensor, labels: Tensor, idx: Tensor, nb_fwd, nb_bwd: int, adam,
-                 slot: int):
+    def _capture(self, ent: dict, features: Tensor, labels: Tensor, idx: Tensor, cfg, adam, slot: int):
         (p, m, v), (lr, b1, b2, eps, wd, step, dec) = adam
         dev = self.flat.grad.device
-        hw, hb = self.m.fc.weight, self.m.fc.bias
         ent["idx"] = idx.clone()
         # statistics go straight into the epoch ring: row = device step count
         # (before this step's Adam advances it) + slot_off
@@ -524,11 +505,8 @@ class MotionTrainStep:
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            nb, sp = nb_fwd  # (sequences per forward workgroup, forward lanes per unit)
-            ws, feats, cell = self._operands(features)  # GRU: the re-pack is part of the graph
-            self.mod.lstm_head_train_step(feats, ent["idx"], labels, ws, hw, hb, self.flat.grad, self.ring,
-                                          self.H, self.NL, sp, 0, nb, nb_bwd, None, None, cell, self.colmap,
-                                          ent["step"], ent["slot_off"], round_bf16=self.bf16)
+            # (GRU: the re-pack is part of the graph)
+            self._launch(features, ent["idx"], labels, self.ring, cfg, step=ent["step"], slot_off=ent["slot_off"])
             self.grad_sync()
             self.mod.adam_flat(p, self.flat.grad, m, v, None, lr, b1, b2, eps, wd, step, 1.0, bool(dec), False,
                                None, ent["step"], ent["ticket"])

@@ -53,6 +53,63 @@ def test_uncovered_shapes_run_on_hip(cell, H, L, bidir):
     _check(ref, mod, torch.randn(B, T, I, dtype=torch.float64))
 
 
+@pytest.mark.parametrize("cell,H,L,opt", [
+    ("lstm", 24, 3, "state"), ("gru", 8, 2, "state"),          # h0 (and c0) into a padded, chunked stack
+    ("lstm", 32, 2, "no_bias"), ("gru", 32, 2, "no_bias"),
+    ("lstm", 48, 2, "time_first"),                             # time-first input on a padded stack
+    ("lstm", 32, 5, "idx"), ("lstm", 32, 5, "nograd"),         # two chunks: in-kernel gather; need_out=False
+])
+def test_stack_options_run_on_hip(cell, H, L, opt):
+    """What the small-H stack runner passes along besides the shape -- initial
+    states, absent biases, the time-first layout, the batch gather (first
+    chunk only) and the inference launch that streams no output -- against
+    fp64 modules at _check's tolerances, input and state gradients included."""
+    from pytorch_distributed_rnn_amd.models.rnn import GRU, LSTM
+    torch.manual_seed(0)
+    I, B, T = 9, 6, 33
+    lstm, dev = cell == "lstm", torch.device("cuda")
+    kw = dict(bias=opt != "no_bias", batch_first=opt != "time_first")
+    ref = (torch.nn.LSTM if lstm else torch.nn.GRU)(I, H, L, **kw).double()
+    mod = (LSTM if lstm else GRU)(I, H, L, **kw).cuda()
+    mod.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    N = B + 3 if opt == "idx" else B
+    x = torch.randn((T, N, I) if opt == "time_first" else (N, T, I), dtype=torch.float64, requires_grad=True)
+    idx = torch.randperm(N)[:B] if opt == "idx" else None
+    st = [torch.randn(L, B, H, dtype=torch.float64, requires_grad=True) for _ in range(2 if lstm else 1)] \
+        if opt == "state" else []
+    xg = x.detach().float().to(dev).requires_grad_(idx is None)  # (no input gradient through the gather)
+    stg = [s.detach().float().to(dev).requires_grad_() for s in st]
+
+    def hx(s):
+        return None if not s else (tuple(s) if lstm else s[0])
+
+    def states(res):
+        return list(res) if lstm else [res]
+
+    out_ref, res_ref = ref(x if idx is None else x[idx], hx(st))
+    if opt == "nograd":
+        with torch.no_grad():
+            out, res = mod(xg, need_out=False)
+        assert out is None
+        for a, b in zip(states(res), states(res_ref)):
+            assert (a.double().cpu() - b).abs().max().item() < 2e-4
+        return
+    out, res = mod(xg, hx(stg), **({"idx": idx.to(dev)} if idx is not None else {}))
+    assert (out.double().cpu() - out_ref).abs().max().item() < 2e-4
+    for a, b in zip(states(res), states(res_ref)):
+        assert (a.double().cpu() - b).abs().max().item() < 2e-4
+    g = torch.randn_like(out_ref)
+    ((out_ref * g).sum() + sum(s.square().sum() for s in states(res_ref))).backward()
+    ((out * g.float().to(dev)).sum() + sum(s.square().sum() for s in states(res))).backward()
+    pairs = [(n, p.grad, q.grad) for (n, p), q in zip(mod.named_parameters(), ref.parameters())]
+    pairs += [("dx", xg.grad, x.grad)] * (idx is None)
+    pairs += [(f"dstate{k}", a.grad, b.grad) for k, (a, b) in enumerate(zip(stg, st))]
+    for n, got, want in pairs:
+        scale = want.abs().max().item() + 1e-6
+        e = (got.double().cpu() - want).abs().max().item()
+        assert e / scale < 5e-4, (n, e, scale)
+
+
 def test_motion_cli_shapes_train_on_hip(tmp_path):
     """main.py-equivalent model builds with the reference's flags train a step
     through the kernels (strict mode), dropout between layer chunks included."""

@@ -659,7 +659,7 @@ class _Call:
 
     def __init__(self, case, monkeypatch):
         from pytorch_distributed_rnn_amd.ops import gru_fused
-        from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+        from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
         c, s = case, _operands(case)
         self.case, self.s, self.mod = c, s, _mod()
         dev = torch.device("cuda")
@@ -671,8 +671,8 @@ class _Call:
         set_tune(monkeypatch, dwout=c.dwout, dwout_nb=None, split_fwd=None, split_bwd=None,
                  sw_mode=str(c.fm) if c.fm >= 0 else None, sw_bwd_mode=str(c.bm) if c.bm >= 0 else None,
                  nb_bwd=str(c.nb_bwd) if c.nb_bwd else None, nb_fwd=str(c.nb_fwd) if c.nb_fwd else None)
-        self.nb_fwd, self.sp_fwd, _, _ = small_launch_config(c.B, c.H, c.NL)
-        self.nb_bwd = fused_bwd_nb(c.B, c.H, c.NL)
+        # (the LSTM's config for either cell: the table pins what differs through PDRNN_TUNE)
+        (self.nb_fwd, self.sp_fwd), self.nb_bwd = step_launch_config(LSTM, c.B, c.H, c.NL)
         assert (self.nb_fwd, self.nb_bwd) == (max(c.nb_fwd, 1), max(c.nb_bwd, 1))
         plan = self.mod.lstm_head_step_plan(c.H, c.I, c.NL, c.T, c.B, cell=c.cell, nb_fwd=self.nb_fwd,
                                             split_fwd=self.sp_fwd, nb_bwd=self.nb_bwd, split_bwd=0)
@@ -966,7 +966,7 @@ def test_tags_that_ran(monkeypatch):
     recorded are the same set.  A plan change that reroutes a case fails here
     and in that case's own assertion."""
     mod = _mod()
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     seen = set()
     for c in CASES:
         if c.sw_env is None:
@@ -976,9 +976,9 @@ def test_tags_that_ran(monkeypatch):
         set_tune(monkeypatch, dwout=c.dwout, dwout_nb=None, split_fwd=None, split_bwd=None,
                  sw_mode=str(c.fm) if c.fm >= 0 else None, sw_bwd_mode=str(c.bm) if c.bm >= 0 else None,
                  nb_bwd=str(c.nb_bwd) if c.nb_bwd else None, nb_fwd=str(c.nb_fwd) if c.nb_fwd else None)
-        nb_fwd, sp_fwd, _, _ = small_launch_config(c.B, c.H, c.NL)
+        (nb_fwd, sp_fwd), nb_bwd = step_launch_config(LSTM, c.B, c.H, c.NL)
         p = mod.lstm_head_step_plan(c.H, c.I, c.NL, c.T, c.B, cell=c.cell, nb_fwd=nb_fwd, split_fwd=sp_fwd,
-                                    nb_bwd=fused_bwd_nb(c.B, c.H, c.NL), split_bwd=0)
+                                    nb_bwd=nb_bwd, split_bwd=0)
         tag = f"{p['path']} {CELLS[c.cell]} H{c.H}"
         if p["sw"]:
             tag += f" f{p['sw_fmode']} b{p['sw_bmode']}"

@@ -343,6 +343,6 @@ def test_fused_gru_streamed_x_matches_torch(H, NL, I, B, T, nb_fwd, monkeypatch)
 
 def test_fused_gru_really_runs():
     # the HIP path, not the ATen fallback, must serve this shape
-    from pytorch_distributed_rnn_amd.ops import gru_fused
+    from pytorch_distributed_rnn_amd.ops.lstm import small_plan
     x = torch.randn(4, 10, 9, device="cuda")
-    assert gru_fused.supported(x, 32, 2)
+    assert small_plan(x, 32, 2, cell="gru") == (32, [(0, 2)])  # one unpadded launch

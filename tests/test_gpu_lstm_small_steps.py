@@ -437,7 +437,7 @@ def _forward_case(H, NL, cell, nb, split, save, T, B, variant, seed, wscale=1.0)
     need_out = v.pop("need_out", True)
     s = _inputs(H, NL, cell, B, T, v.pop("I"), seed, wscale=wscale, **v)
     if cell == 1:
-        assert gru_fused.supported(s.x_ref, H, NL)
+        assert lstm_ops.small_plan(s.x_ref, H, NL, cell="gru") == (H, [(0, NL)])  # one unpadded launch
     out, hn, cn, act = mod.lstm_small_fwd(s.x, s.idx, s.w, s.h0, s.c0, H, NL, s.batch_first, save, need_out, nb,
                                           split, cell)
     torch.cuda.synchronize()
@@ -591,7 +591,7 @@ def _bwd_matrix():
         for H, NL in shapes:
             for name in _BWD_VARIANTS:
                 if name == "bf16" and (split == 2 or cell == 1):
-                    continue  # refused (test_refusals) / fp32 only (gru_fused.supported)
+                    continue  # refused (test_refusals) / fp32 only (ops.lstm.GRU.dtypes)
                 rows.append(pytest.param(split, cell, nb, H, NL, name,
                                          id=f"{'unit' if split == 1 else 'rowsplit'}-{CELLS[cell]}-nb{nb}-H{H}x{NL}-{name}"))
     return rows

@@ -24,13 +24,13 @@ def _mod():
 def _fused_grads(model, train, B, round_bf16=False):
     """Gradients of one fused step (no optimizer update) on the first batch,
     the batch gathered through the loader's index vector."""
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     from pytorch_distributed_rnn_amd.train.trainer import Trainer
     t = Trainer(model, train, batch_size=B, learning_rate=2.5e-3, device=torch.device("cuda"))
     f = t._fused_step()
     assert f is not None
     feats, labels, idx = t.train_loader.make_batch(t.train_loader.batch_indices()[0])
-    nb_f, sp_f, _, _ = small_launch_config(idx.numel(), f.H, f.NL)
+    (nb_f, sp_f), nb_b = step_launch_config(LSTM, idx.numel(), f.H, f.NL)
     ws = f.weights
     if f.gru:
         from pytorch_distributed_rnn_amd.ops.gru_fused import _pack
@@ -40,7 +40,7 @@ def _fused_grads(model, train, B, round_bf16=False):
     f.flat.grad.zero_()
     stats = torch.zeros(3, device="cuda")
     f.mod.lstm_head_train_step(feats, idx, labels, ws, f.m.fc.weight, f.m.fc.bias, f.flat.grad, stats, f.H, f.NL,
-                               sp_f, 0, nb_f, fused_bwd_nb(idx.numel(), f.H, f.NL), None, None,
+                               sp_f, 0, nb_f, nb_b, None, None,
                                1 if f.gru else 0, f.colmap, round_bf16=round_bf16)
     return [p.grad.detach().double() for p in f.m.parameters()], feats.index_select(0, idx), \
         labels.index_select(0, idx).reshape(-1), f.flat.grad.detach().clone()

@@ -116,17 +116,15 @@ def test_step_plan_agrees_with_selection_queries(monkeypatch):
     query bindings (which ask it about the gate-split / K-split family), and
     names the expected one of the five paths."""
     from pytorch_distributed_rnn_amd import _ext
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     mod = _ext.native(torch.device("cuda", 0))
     H, I, NL, T = 32, 9, 2, 128
 
     def plan(B, **kw):
-        nb_f, sp_f, _, sp_b = small_launch_config(B, H, NL)
-        p = mod.lstm_head_step_plan(H, I, NL, T, B, nb_fwd=nb_f, split_fwd=sp_f, nb_bwd=fused_bwd_nb(B, H, NL),
-                                    split_bwd=sp_b, **kw)
+        (nb_f, sp_f), nb_b = step_launch_config(LSTM, B, H, NL)
+        p = mod.lstm_head_step_plan(H, I, NL, T, B, nb_fwd=nb_f, split_fwd=sp_f, nb_bwd=nb_b, split_bwd=0, **kw)
         if not p["sw"]:
-            assert p["one_launch"] == mod.lstm_small_step_one_launch(H, NL, T, B, nb_f, sp_f, fused_bwd_nb(B, H, NL),
-                                                                     sp_b), B
+            assert p["one_launch"] == mod.lstm_small_step_one_launch(H, NL, T, B, nb_f, sp_f, nb_b, 0), B
             assert p["dwout"] == mod.lstm_small_step_deferred_dw(H, NL, T, B), B
             if p["dwout"]:
                 assert (p["nb_dw"], p["grid_dw"]) == mod.lstm_small_dwout_geometry(H, NL, T, B), B
@@ -159,11 +157,11 @@ def test_one_launch_step_selected_in_latency_regime():
     (the B=96 runs of test_fused_step_matches_autograd go through it); the
     headline B=1440 keeps the separate launches."""
     from pytorch_distributed_rnn_amd import _ext
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     mod = _ext.native(torch.device("cuda", 0))
     for b, expect in ((96, True), (180, True), (1440, False)):
-        nb_f, sp_f, _, sp_b = small_launch_config(b, 32, 2)
-        got = mod.lstm_small_step_one_launch(32, 2, 128, b, nb_f, sp_f, fused_bwd_nb(b, 32, 2), sp_b)
+        (nb_f, sp_f), nb_b = step_launch_config(LSTM, b, 32, 2)
+        got = mod.lstm_small_step_one_launch(32, 2, 128, b, nb_f, sp_f, nb_b, 0)
         assert got == expect, (b, got)
 
 
@@ -271,13 +269,13 @@ def test_deferred_dw_backward_matches_autograd(cell, hidden, layers, seq, featur
 
 def _fused_grads(model, train, B):
     """Gradients of one fused step (no optimizer update) on the first batch."""
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     from pytorch_distributed_rnn_amd.train.trainer import Trainer
     t = Trainer(model, train, batch_size=B, learning_rate=2.5e-3, device=torch.device("cuda"))
     f = t._fused_step()
     assert f is not None
     feats, labels, idx = t.train_loader.make_batch(t.train_loader.batch_indices()[0])
-    nb_f, sp_f, _, _ = small_launch_config(idx.numel(), f.H, f.NL)
+    (nb_f, sp_f), nb_b = step_launch_config(LSTM, idx.numel(), f.H, f.NL)
     ws = f.weights
     if f.gru:
         from pytorch_distributed_rnn_amd.ops.gru_fused import _pack
@@ -286,7 +284,7 @@ def _fused_grads(model, train, B):
     f.flat.attach_grads()
     stats = torch.zeros(3, device="cuda")
     f.mod.lstm_head_train_step(feats, idx, labels, ws, f.m.fc.weight, f.m.fc.bias, f.flat.grad, stats, f.H, f.NL,
-                               sp_f, 0, nb_f, fused_bwd_nb(idx.numel(), f.H, f.NL), None, None,
+                               sp_f, 0, nb_f, nb_b, None, None,
                                1 if f.gru else 0, f.colmap)
     return [p.grad.detach().double() for p in f.m.parameters()], feats.index_select(0, idx), \
         labels.index_select(0, idx).reshape(-1)
@@ -456,14 +454,14 @@ def test_one_launch_gradients_match_fp64(cell, B, monkeypatch):
     from pytorch_distributed_rnn_amd import _ext
     from pytorch_distributed_rnn_amd.data.motion import synthetic_motion
     from pytorch_distributed_rnn_amd.models.motion import MotionModel
-    from pytorch_distributed_rnn_amd.ops.lstm import fused_bwd_nb, small_launch_config
+    from pytorch_distributed_rnn_amd.ops.lstm import LSTM, step_launch_config
     monkeypatch.setenv("PDRNN_SW", "0")
     set_tune(monkeypatch, dwout=None)
     mod = _ext.native(torch.device("cuda", 0))
-    nb_f, sp_f, _, sp_b = small_launch_config(B, 32, 2)
+    (nb_f, sp_f), nb_b = step_launch_config(LSTM, B, 32, 2)
     if cell == "gru":
         nb_f, sp_f = 1, 1
-    assert mod.lstm_small_step_one_launch(32, 2, 128, B, nb_f, sp_f, fused_bwd_nb(B, 32, 2), sp_b)
+    assert mod.lstm_small_step_one_launch(32, 2, 128, B, nb_f, sp_f, nb_b, 0)
     torch.manual_seed(21 + B)
     train, _, _ = synthetic_motion(n_train=B, n_validation=2, n_test=2, seed=22)
     _fp64_check(MotionModel(9, 32, 2, 6, cell=cell), train, B)
