@@ -26,8 +26,11 @@ prompt): per width, the reference path, the fused path and plain fused
 sampling of W streams alternate in one process after the warm-up; one JSON
 line per width.
 
+``--cell gru``: the same for a GRU model (``CharLM(cell="gru")``).
+
     python bench/decode_bench.py [--pairs 5] [--warmup 2] [--tokens 512] [--batches 1 4 16] [--out FILE]
                                  [--top-k 40] [--top-p 0.9] [--logprobs] [--beam-width 1 4 16]
+                                 [--cell gru]
 """
 from __future__ import annotations
 
@@ -77,7 +80,8 @@ def beam(args, model, dec, dev, cdt, generate) -> int:
 
     lines = []
     for W in args.beam_width:
-        assert real(1, W, args.hidden, args.embed, args.vocab, args.layers, cdt, dev), f"the decode kernels do not cover W = {W}"
+        assert real(1, W, args.hidden, args.embed, args.vocab, args.layers, cdt, dev, args.cell), \
+            f"the decode kernels do not cover W = {W}"
         streams = torch.zeros(W, 1, dtype=torch.int64, device=dev)
         calls = {"reference": lambda: search(W, False), "fused": lambda: search(W, True),
                  "sampling": lambda: generate(streams, True)}
@@ -85,7 +89,7 @@ def beam(args, model, dec, dev, cdt, generate) -> int:
             outs = {k: f() for k, f in calls.items()}
         rounds = [{k: timed(f) for k, f in calls.items()} for _ in range(args.pairs)]
         rec = {"beam_width": W, "tokens": args.tokens,
-               "model": f"{args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
+               "model": f"{args.cell} {args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
                "rounds_us_per_token": [{k: round(v, 2) for k, v in r.items()} for r in rounds]}
         for k in calls:
             rec[k + "_us_per_token"] = summary([r[k] for r in rounds])
@@ -118,6 +122,7 @@ def main(argv=None) -> int:
     ap.add_argument("--logprobs", action="store_true", help="also return the tokens' log-probabilities")
     ap.add_argument("--beam-width", type=int, nargs="+", default=None, metavar="W",
                     help="time beam search at these widths instead (one prompt per call)")
+    ap.add_argument("--cell", choices=("lstm", "gru"), default="lstm")
     ap.add_argument("--profile-one", type=int, default=None, metavar="B")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args(argv)
@@ -129,8 +134,9 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", 0)
     cdt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     torch.manual_seed(0)
-    model = CharLM(args.vocab, args.embed, args.hidden, args.layers, compute_dtype=cdt).to(dev).eval()
+    model = CharLM(args.vocab, args.embed, args.hidden, args.layers, compute_dtype=cdt, cell=args.cell).to(dev).eval()
     real_supported = dec.supported
+    covered = lambda B: real_supported(B, args.hidden, args.embed, args.vocab, args.layers, cdt, dev, args.cell)  # noqa: E731
 
     def generate(prompt, fused: bool):
         # the reference path is generate's own: the shape reported as not covered
@@ -158,7 +164,7 @@ def main(argv=None) -> int:
 
     if args.profile_one is not None:
         prompt = torch.zeros(args.profile_one, 1, dtype=torch.int64, device=dev)
-        assert real_supported(args.profile_one, args.hidden, args.embed, args.vocab, args.layers, cdt, dev)
+        assert covered(args.profile_one)
         for _ in range(args.warmup):
             generate(prompt, False), generate(prompt, True)
         print(json.dumps({"profile_one": args.profile_one, "tokens": args.tokens, "top_k": args.top_k,
@@ -170,13 +176,12 @@ def main(argv=None) -> int:
     lines = []
     for B in args.batches:
         prompt = torch.zeros(B, 1, dtype=torch.int64, device=dev)
-        assert real_supported(B, args.hidden, args.embed, args.vocab, args.layers, cdt, dev), \
-            f"the decode kernels do not cover B = {B}"
+        assert covered(B), f"the decode kernels do not cover B = {B}"
         for _ in range(args.warmup):
             ref, new = generate(prompt, False), generate(prompt, True)
         pairs = [(timed(prompt, False), timed(prompt, True)) for _ in range(args.pairs)]
         old, fused = [p[0] for p in pairs], [p[1] for p in pairs]
-        rec = {"B": B, "tokens": args.tokens, "model": f"{args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
+        rec = {"B": B, "tokens": args.tokens, "model": f"{args.cell} {args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
                "top_k": args.top_k, "top_p": args.top_p, "logprobs": args.logprobs,
                "pairs_us_per_token": [[round(a, 2), round(b, 2)] for a, b in pairs],
                "reference_us_per_token": {"median": round(statistics.median(old), 2), "min": round(min(old), 2),

@@ -1812,11 +1812,12 @@ struct DecodeStack {
   DecodeStack(const DecodeStack&) = delete;
 };
 
-// The checks lstm_decode and lstm_decode_beam share, `what` the message prefix:
-// the stack's weights and the working buffers of B = h.size(2) streams and N positions.
+// The checks the decode bindings share, `what` the message prefix: the stack's
+// weights (cell: PdrnnLstmDecodeStack's) and the working buffers of B = h.size(2)
+// streams and N positions.
 // They run before the search's own G / W checks, so a search with too many
 // streams is refused here as "unsupported shape B=..." (B: its S = G W).
-DecodeStack check_decode_stack(const char* what, const Tensor& emb, const std::vector<Tensor>& w_ih,
+DecodeStack check_decode_stack(const char* what, int cell, const Tensor& emb, const std::vector<Tensor>& w_ih,
                                const std::vector<Tensor>& w_hh, const std::vector<Tensor>& bias, const Tensor& w_fc,
                                const optional<Tensor>& b_fc, const Tensor& h, const Tensor& c, const Tensor& scratch,
                                const Tensor& first, const optional<Tensor>& logits, int64_t N) {
@@ -1827,7 +1828,9 @@ DecodeStack check_decode_stack(const char* what, const Tensor& emb, const std::v
   TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
               what, ": h [2, L, B, H] in the weights' dtype");
   const int64_t B = h.size(2), H = h.size(3);
-  TORCH_CHECK(pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt) && N >= 1,
+  const bool fits = cell == 0 ? pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt)
+                              : pdrnn_gru_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt);
+  TORCH_CHECK(fits && N >= 1,
               what, ": unsupported shape B=", B, " H=", H, " E=", E, " V=", V, " L=", L, " N=", N);
   DecodeStack d;
   auto weight = [&](const Tensor& w, int64_t rows, int64_t cols) {
@@ -1862,31 +1865,39 @@ DecodeStack check_decode_stack(const char* what, const Tensor& emb, const std::v
   s.logits = opt_mut(logits);
   s.B = (int)B; s.H = (int)H; s.E = (int)E; s.V = (int)V; s.L = (int)L;
   s.dtype = dt;
+  s.cell = cell;
   return d;
 }
 
 // Char-LM generation (kernels/lstm_decode.hip): n_tokens positions of the
 // decode kernels, enqueued here in one go.  The buffers are the caller's (ops/decode.py).
-void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
+// CELL (PdrnnLstmDecodeStack's): _C.lstm_decode and _C.gru_decode (ops/gru_large.py's
+// zero-padded interleaved [4H, .] stacks; c: h's fp32 master).
+constexpr const char* kDecodeName[] = {"lstm_decode", "gru_decode"};
+constexpr const char* kDecodeBeamName[] = {"lstm_decode_beam", "gru_decode_beam"};
+
+template <int CELL>
+void decode_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
                  const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
                  const Tensor& c, const Tensor& scratch, const Tensor& first, const optional<Tensor>& forced,
                  const Tensor& tokens, const optional<Tensor>& logits, double temperature, int64_t seed,
                  int64_t stream0, int64_t pos0, int64_t top_k, double top_p, const optional<Tensor>& threshold,
                  const optional<Tensor>& logprobs) {
+  const char* what = kDecodeName[CELL];
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
   const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
-  const DecodeStack d = check_decode_stack("lstm_decode", emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+  const DecodeStack d = check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
   const int64_t B = d.stack.B;
-  TORCH_CHECK(dev_i64(tokens) && tokens.size(0) == B, "lstm_decode: tokens [B, N] int64");
+  TORCH_CHECK(dev_i64(tokens) && tokens.size(0) == B, what, ": tokens [B, N] int64");
   if (present(forced)) TORCH_CHECK(dev_i64(*forced) && forced->dim() == 2 && forced->size(0) == B && forced->size(1) == N,
-                                   "lstm_decode: forced [B, N] int64");
-  TORCH_CHECK(temperature >= 0.0, "lstm_decode: temperature >= 0");
-  TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, "lstm_decode: top_k >= 0 (0: off)");
-  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "lstm_decode: top_p in (0, 1] (1: off)");
+                                   what, ": forced [B, N] int64");
+  TORCH_CHECK(temperature >= 0.0, what, ": temperature >= 0");
+  TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, what, ": top_k >= 0 (0: off)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, what, ": top_p in (0, 1] (1: off)");
   for (const optional<Tensor>* o : {&threshold, &logprobs})
     if (present(*o)) TORCH_CHECK(dev_f32(**o) && (*o)->dim() == 2 && (*o)->size(0) == B && (*o)->size(1) == N,
-                                 "lstm_decode: threshold / logprobs [B, N] fp32, contiguous, on the device");
+                                 what, ": threshold / logprobs [B, N] fp32, contiguous, on the device");
   PdrnnLstmDecodeArgs a{};
   a.stack = d.stack;
   a.forced = present(forced) ? forced->data_ptr<int64_t>() : nullptr;
@@ -1904,34 +1915,37 @@ void lstm_decode(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
 
 // Beam search on the decode kernels: G groups of W beams; the buffers are the
 // caller's (ops/decode.py:alloc_beam_buffers), cum / done row 0 filled.
-void lstm_decode_beam(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
+template <int CELL>
+void decode_beam_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
                       const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
                       const Tensor& c, const Tensor& scratch, const Tensor& first, const Tensor& cum, const Tensor& done,
                       const Tensor& tokens, const Tensor& parents, const optional<Tensor>& lp,
                       const optional<Tensor>& logits, const Tensor& hyp, const optional<Tensor>& hyp_lp, int64_t G,
                       int64_t W, int64_t stop) {
+  const char* what = kDecodeBeamName[CELL];
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
   const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
   const DecodeStack d =
-      check_decode_stack("lstm_decode_beam", emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+      check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
   const PdrnnLstmDecodeStack& s = d.stack;
   const int64_t S = s.B;
   TORCH_CHECK(G >= 1 && W >= 1 && G <= 16 && W <= 16 && G * W == S &&
-              pdrnn_lstm_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype),
-              "lstm_decode_beam: unsupported shape G=", G, " W=", W, " S=", S, " H=", s.H, " E=", s.E, " V=", s.V,
+              (CELL == 0 ? pdrnn_lstm_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype)
+                         : pdrnn_gru_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype)),
+              what, ": unsupported shape G=", G, " W=", W, " S=", S, " H=", s.H, " E=", s.E, " V=", s.V,
               " L=", s.L, " N=", N);
-  TORCH_CHECK(stop >= -1 && stop < s.V, "lstm_decode_beam: stop in [0, V), or -1 for none");
+  TORCH_CHECK(stop >= -1 && stop < s.V, what, ": stop in [0, V), or -1 for none");
   auto sn = [&](const Tensor& t) { return t.dim() == 2 && t.size(0) == S && t.size(1) == N; };
   TORCH_CHECK(dev_f32(cum) && cum.dim() == 2 && cum.size(0) == N + 1 && cum.size(1) == S,
-              "lstm_decode_beam: cum [N + 1, S] fp32");
+              what, ": cum [N + 1, S] fp32");
   TORCH_CHECK(dev_i32(done) && done.dim() == 2 && done.size(0) == N + 1 && done.size(1) == S,
-              "lstm_decode_beam: done [N + 1, S] int32");
-  TORCH_CHECK(dev_i64(tokens) && sn(tokens) && dev_i64(hyp) && sn(hyp), "lstm_decode_beam: tokens / hyp [S, N] int64");
-  TORCH_CHECK(dev_i32(parents) && sn(parents), "lstm_decode_beam: parents [S, N] int32");
+              what, ": done [N + 1, S] int32");
+  TORCH_CHECK(dev_i64(tokens) && sn(tokens) && dev_i64(hyp) && sn(hyp), what, ": tokens / hyp [S, N] int64");
+  TORCH_CHECK(dev_i32(parents) && sn(parents), what, ": parents [S, N] int32");
   for (const optional<Tensor>* o : {&lp, &hyp_lp})
-    if (present(*o)) TORCH_CHECK(dev_f32(**o) && sn(**o), "lstm_decode_beam: lp / hyp_lp [S, N] fp32");
-  TORCH_CHECK(!present(hyp_lp) || present(lp), "lstm_decode_beam: hyp_lp needs lp");
+    if (present(*o)) TORCH_CHECK(dev_f32(**o) && sn(**o), what, ": lp / hyp_lp [S, N] fp32");
+  TORCH_CHECK(!present(hyp_lp) || present(lp), what, ": hyp_lp needs lp");
   PdrnnLstmDecodeBeamArgs a{};
   a.stack = s;
   a.cum = cum.data_ptr<float>();
@@ -2187,20 +2201,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "128x128 slices instead of 32x32, ping-pong GEMM + cell pair");
   m.def("lstm_large_bwd", &lstm_large_bwd, "large-H LSTM layer BPTT (MFMA step kernels) -> dgates, dh0, dc0");
   m.def("lstm_large_supported", [](int64_t H) { return pdrnn_lstm_large_supported((int)H) != 0; });
-  m.def("lstm_decode", &lstm_decode, "char-LM generation: n_tokens positions of the fused decode kernels",
-        py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
-        py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("forced"), py::arg("tokens"),
-        py::arg("logits"), py::arg("temperature"), py::arg("seed"), py::arg("stream0"), py::arg("pos0"),
-        py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("threshold") = py::none(),
-        py::arg("logprobs") = py::none());
+  auto def_decode = [&m](const char* name, auto fn, const char* doc) {
+    m.def(name, fn, doc, py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"),
+          py::arg("b_fc"), py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("forced"),
+          py::arg("tokens"), py::arg("logits"), py::arg("temperature"), py::arg("seed"), py::arg("stream0"),
+          py::arg("pos0"), py::arg("top_k") = 0, py::arg("top_p") = 1.0, py::arg("threshold") = py::none(),
+          py::arg("logprobs") = py::none());
+  };
+  def_decode("lstm_decode", &decode_cell<0>, "char-LM generation: n_tokens positions of the fused decode kernels");
+  def_decode("gru_decode", &decode_cell<1>, "lstm_decode for a GRU stack: padded [4H, .] stacks, c the fp32 master of h");
+  auto def_supported = [&m](const char* name, int (*fn)(int, int, int, int, int, int)) {
+    m.def(name, [fn](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
+      return fn((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
+    }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
+  };
+  def_supported("gru_decode_supported", &pdrnn_gru_decode_supported);
   m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
     return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
   }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
-  m.def("lstm_decode_beam", &lstm_decode_beam, "char-LM beam search: n_tokens positions of the fused decode kernels",
-        py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"), py::arg("b_fc"),
-        py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("cum"), py::arg("done"),
-        py::arg("tokens"), py::arg("parents"), py::arg("lp"), py::arg("logits"), py::arg("hyp"), py::arg("hyp_lp"),
-        py::arg("G"), py::arg("W"), py::arg("stop") = -1);
+  auto def_beam = [&m](const char* name, auto fn, const char* doc) {
+    m.def(name, fn, doc, py::arg("emb"), py::arg("w_ih"), py::arg("w_hh"), py::arg("bias"), py::arg("w_fc"),
+          py::arg("b_fc"), py::arg("h"), py::arg("c"), py::arg("scratch"), py::arg("first"), py::arg("cum"),
+          py::arg("done"), py::arg("tokens"), py::arg("parents"), py::arg("lp"), py::arg("logits"), py::arg("hyp"),
+          py::arg("hyp_lp"), py::arg("G"), py::arg("W"), py::arg("stop") = -1);
+  };
+  def_beam("lstm_decode_beam", &decode_beam_cell<0>, "char-LM beam search: n_tokens positions of the fused decode kernels");
+  def_beam("gru_decode_beam", &decode_beam_cell<1>, "lstm_decode_beam for a GRU stack (gru_decode's operands)");
+  m.def("gru_decode_beam_supported",
+        [](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
+          auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
+          return fits(G) && fits(W) && fits(H) && fits(E) && fits(V) && fits(L) &&
+                 pdrnn_gru_decode_beam_supported((int)G, (int)W, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
+        }, "the decode kernels cover a GRU beam search of G groups of W beams (dtype 0 bf16, 1 fp16, 2 fp32)");
   m.def("lstm_decode_beam_supported",
         [](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
           auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };

@@ -479,7 +479,12 @@ hipError_t pdrnn_slab_reduce_adam(const PdrnnAdamArgs* a, const float* A, int64_
 // ---- char-LM generation (kernels/lstm_decode.hip) --------------------------
 // One token of a unidirectional 16-bit LSTM stack with biases for B <= 16
 // streams is L launches of the decode layer kernel plus one of the vocabulary
-// head.  The stack and its working buffers, common to sampling and beam search:
+// head.  The stack and its working buffers, common to sampling and beam search.
+// cell 1 is a GRU stack on the same launches: w_ih / w_hh are then the
+// zero-padded gate-interleaved stacks [r | z | n_x | 0] and [r | z | 0 | n_h]
+// (rows 4u + q: ops/gru_large.py), bias is [b_ir + b_hr, b_iz + b_hz, b_in,
+// b_hn] per unit, and c holds h in fp32 (h_t = n + z (h_{t-1} - n) on it, in
+// place), of which h is the rounding.
 typedef struct {
   const void* emb;           // [V, E] embedding, 16-bit
   const void* const* w_ih;   // host array [L]: [4H, E] (layer 0) / [4H, H], gate-interleaved rows 4u + q, 16-bit
@@ -494,6 +499,7 @@ typedef struct {
   float* logits;             // [B, n_tokens, V] or NULL: per stream and position
   int B, H, E, V, L;         // B: the streams of the launch (the search's G W)
   int dtype;                 // 0 bf16, 1 fp16
+  int cell;                  // 0 LSTM, 1 GRU
 } PdrnnLstmDecodeStack;
 
 // Sampling: position p's input token is forced[b, p] if forced is given, else
@@ -519,6 +525,9 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype);
 // read.  Every 16-bit pointer 16-byte aligned.  top_k < 0 and a negative or
 // NaN top_p are hipErrorInvalidValue.
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
+// the limits of a GRU stack (cell 1) in pdrnn_lstm_decode / pdrnn_lstm_decode_beam: the LSTM's
+int pdrnn_gru_decode_supported(int B, int H, int E, int V, int L, int dtype);
+int pdrnn_gru_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype);
 
 // Beam search on the same kernels (pdrnn/decode_rng.h: the rule): G groups of W
 // beams, S = G W <= 16 streams, stream g W + j beam j of group g.  Selection q

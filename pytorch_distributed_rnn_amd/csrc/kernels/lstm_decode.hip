@@ -34,8 +34,21 @@
 // one token loop on the host (decode_positions) and differ in the layer-0
 // instantiation and in the launch after the last position.
 //
-// Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) +
-// nn.Linear stepped one token at a time.
+// The GRU (Cell::gru) is the same launches with another cell.  A unit's four A
+// rows are r, z, n_x, n_h: the n gate's input and recurrent parts land in
+// separate accumulator registers of one lane, and n = tanh(n_x + b_in + r (n_h
+// + b_hn)) again needs no exchange.  n_h has no x part and n_x no h part: the
+// rows come from the training kernels' zero-padded gate-interleaved stacks
+// ([r | z | n_x | 0] and [r | z | 0 | n_h], ops/gru_large.py), read exactly as
+// the LSTM's.  (Leaving the zero quarter unread -- the lanes of that row slot
+// predicated off, rows straight from nn.GRU's [3H, .] -- measured slower at
+// B = 1 and B = 16: profiles/r18/gru_decode.md.)  h_t = n + z (h_{t-1} - n)
+// reads h_{t-1} from an fp32 master, which lives where the LSTM keeps c
+// (LayerArgs::c) and is updated in place like it; the 16-bit ping-pong h is
+// its rounding.
+//
+// Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) or
+// nn.GRU (r, z, n) + nn.Linear stepped one token at a time.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -464,13 +477,13 @@ __device__ __forceinline__ int beam_parent(int par, int n, int W) {
 }
 
 struct LayerArgs {
-  const uint16_t* wx;     // [4H, Kx] gate-interleaved rows 4u + q
-  const uint16_t* wh;     // [4H, H]
-  const float* bias;      // [4H] b_ih + b_hh, interleaved
+  const uint16_t* wx;     // [4H, Kx] gate-interleaved rows 4u + q (GRU: q = r, z, n_x, 0)
+  const uint16_t* wh;     // [4H, H] (GRU: q = r, z, 0, n_h)
+  const float* bias;      // [4H] b_ih + b_hh, interleaved; GRU: b_ir + b_hr, b_iz + b_hz, b_in, b_hn per unit
   const uint16_t* x;      // FIRST: the embedding [V, Kx]; else the layer below's h_t [B, Kx]
   const uint16_t* hprev;  // [B, H]
   uint16_t* hout;         // [B, H]
-  float* c;               // [B, H], updated in place
+  float* c;               // [B, H], updated in place: c, or the GRU's fp32 h
   const int64_t* first;   // FIRST: [B] input tokens of position 0
   const int64_t* forced;  // FIRST: [B, N] input tokens of every position, or null
   SampleArgs s;
@@ -481,6 +494,9 @@ struct LayerArgs {
 // How position p's input token is chosen in layer 0.  The layers above read
 // only "beam or not" from it: they exist for sample and beam.
 enum class Pick { sample, filtered, beam };
+
+// The stack's cell (PdrnnLstmDecodeStack::cell): what a lane does with its four sums.
+enum class Cell { lstm = 0, gru = 1 };
 
 // Sum of the waves' partial accumulators, in wave order, into wave 0.
 __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
@@ -498,17 +514,18 @@ __device__ __forceinline__ f32x4 reduce_waves(f32x4 acc, f32x4 (*red)[kWave]) {
 // runs it.
 //
 // Pick::beam: stream n continues stream par = parent[n] of the previous
-// position: it reads h_{t-1} and c of par in every layer (x of a layer above 0
-// is the layer below's h_t, already in new-slot order).  Layer 0 selects
-// (beam_select; by every workgroup, recorded by workgroup 0); the layers above
-// read the record.  c stays in place: a unit's 16 streams are 16 lanes of wave
-// 0 of one workgroup, which loads c[par] in one instruction and stores c[n] in
-// a later one that depends on the loaded value, so every lane's load has
-// completed before any lane's store; no other workgroup touches the unit.
+// position: it reads h_{t-1} and c (the GRU: the fp32 h) of par in every layer
+// (x of a layer above 0 is the layer below's h_t, already in new-slot order).
+// Layer 0 selects (beam_select; by every workgroup, recorded by workgroup 0);
+// the layers above read the record.  c stays in place, for both cells: a unit's
+// 16 streams are 16 lanes of wave 0 of one workgroup, which loads c[par] in one
+// instruction and stores c[n] in a later one that depends on the loaded value,
+// so every lane's load has completed before any lane's store; no other
+// workgroup touches the unit.
 //
 // Every __syncthreads() below is reached by all threads of a workgroup: what
 // guards the sampling and the selection (p, forced, blockIdx) is uniform in it.
-template <class DT, bool FIRST, Pick PICK>
+template <class DT, bool FIRST, Pick PICK, Cell CELL>
 __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a) {
   static_assert(FIRST || PICK != Pick::filtered, "the filter is layer 0's");
   constexpr bool FILT = PICK == Pick::filtered, BEAM = PICK == Pick::beam;
@@ -558,14 +575,14 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   // K blocks of 32: [0, Kx / 32) from x and W_ih, the rest from h_{t-1} and
   // W_hh; wave w takes blocks w, w + 8, ...  Lane: weight row lane & 15 (A),
   // stream lane & 15 (B), k = 8 (lane >> 4) + 0..7 of the block in both.
-  const int row = blockIdx.x * 16 + n;  // < 4H: the grid is H / 4
-  const uint16_t* wxr = a.wx + (int64_t)row * Kx + kq * 8;
-  const uint16_t* whr = a.wh + (int64_t)row * H + kq * 8;
   const uint16_t* xr = xrow + kq * 8;
   const uint16_t* hr = a.hprev + (int64_t)par * H + kq * 8;
   const int nkx = Kx / 32, nkb = nkx + H / 32;
   const uint4 zero = make_uint4(0, 0, 0, 0);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const int row = blockIdx.x * 16 + n;  // < 4H: the grid is H / 4
+  const uint16_t* wxr = a.wx + (int64_t)row * Kx + kq * 8;
+  const uint16_t* whr = a.wh + (int64_t)row * H + kq * 8;
 #pragma unroll 8
   for (int kb = wave; kb < nkb; kb += kWaves) {
     const bool inx = kb < nkx;
@@ -577,17 +594,29 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
   const f32x4 z = reduce_waves(acc, red);
   if (wave != 0 || !live) return;
 
-  // lane: unit 4 blockIdx + (lane >> 4), stream n; z[q] is gate q of it
+  // lane: unit 4 blockIdx + (lane >> 4), stream n; z[q] is gate (GRU: row slot) q of it
   const int u = blockIdx.x * 4 + kq;
   const float* bs = a.bias + 4 * u;
-  const float gi = sigmoidf_fast(z[0] + bs[0]);
-  const float gf = sigmoidf_fast(z[1] + bs[1]);
-  const float gg = tanhf_fast(z[2] + bs[2]);
-  const float go = sigmoidf_fast(z[3] + bs[3]);
   const int64_t at = (int64_t)n * H + u;
-  const float cn = fmaf(gf, a.c[(int64_t)par * H + u], gi * gg);
-  a.c[at] = cn;
-  a.hout[at] = DT::from_f(go * tanhf_fast(cn));
+  if constexpr (CELL == Cell::lstm) {
+    const float gi = sigmoidf_fast(z[0] + bs[0]);
+    const float gf = sigmoidf_fast(z[1] + bs[1]);
+    const float gg = tanhf_fast(z[2] + bs[2]);
+    const float go = sigmoidf_fast(z[3] + bs[3]);
+    const float cn = fmaf(gf, a.c[(int64_t)par * H + u], gi * gg);
+    a.c[at] = cn;
+    a.hout[at] = DT::from_f(go * tanhf_fast(cn));
+  } else {
+    const float gr = sigmoidf_fast(z[0] + bs[0]);
+    const float gz = sigmoidf_fast(z[1] + bs[1]);
+    const float gn = tanhf_fast(fmaf(gr, z[3] + bs[3], z[2] + bs[2]));
+    float hn = fmaf(gz, a.c[(int64_t)par * H + u] - gn, gn);  // h_{t-1} in fp32: the master
+    // the 16-bit h is the rounding of the STORED master: without this the fp16 store is a fused
+    // multiply-add-convert of its own, rounded once, and differs from it in the last place now and then
+    asm volatile("" : "+v"(hn));
+    a.c[at] = hn;
+    a.hout[at] = DT::from_f(hn);
+  }
 }
 
 struct HeadArgs {
@@ -662,8 +691,8 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs
 // the layers above and the head, L + 1 launches on the one stream.  k arrives
 // with the mode's part (s, b, forced) filled in; the caller enqueues the
 // mode's last launch.
-template <class DT, Pick PICK>
-hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, LayerArgs k, hipStream_t stream) {
+template <class DT, Pick PICK, Cell CELL>
+hipError_t decode_positions_of(const PdrnnLstmDecodeStack& a, int n_tokens, LayerArgs k, hipStream_t stream) {
   constexpr Pick ABOVE = PICK == Pick::beam ? Pick::beam : Pick::sample;
   const int B = a.B, H = a.H, V = a.V, L = a.L;
   const uint16_t* h = static_cast<const uint16_t*>(a.h);
@@ -683,8 +712,8 @@ hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, LayerAr
       k.hout = hm + out + l * BH;
       k.c = a.c + l * BH;
       k.Kx = l == 0 ? a.E : H;
-      if (l == 0) lstm_decode_layer<DT, true, PICK><<<H / 4, kThreads, 0, stream>>>(k);
-      else lstm_decode_layer<DT, false, ABOVE><<<H / 4, kThreads, 0, stream>>>(k);
+      if (l == 0) lstm_decode_layer<DT, true, PICK, CELL><<<H / 4, kThreads, 0, stream>>>(k);
+      else lstm_decode_layer<DT, false, ABOVE, CELL><<<H / 4, kThreads, 0, stream>>>(k);
       PDRNN_HIP_CHECK(hipGetLastError());
     }
     const HeadArgs hd{static_cast<const uint16_t*>(a.w_fc), a.b_fc, h + out + (L - 1) * BH, a.scratch, a.logits,
@@ -693,6 +722,21 @@ hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, LayerAr
     PDRNN_HIP_CHECK(hipGetLastError());
   }
   return hipSuccess;
+}
+
+template <class DT, Pick PICK>
+hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, const LayerArgs& k, hipStream_t stream) {
+  switch (a.cell) {
+    case 0: return decode_positions_of<DT, PICK, Cell::lstm>(a, n_tokens, k, stream);
+    case 1: return decode_positions_of<DT, PICK, Cell::gru>(a, n_tokens, k, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+// the stack's limits by its cell
+int stack_supported(const PdrnnLstmDecodeStack& st) {
+  if (st.cell == 0) return pdrnn_lstm_decode_supported(st.B, st.H, st.E, st.V, st.L, st.dtype);
+  return st.cell == 1 && pdrnn_gru_decode_supported(st.B, st.H, st.E, st.V, st.L, st.dtype);
 }
 
 template <class DT>
@@ -735,9 +779,18 @@ int pdrnn_lstm_decode_supported(int B, int H, int E, int V, int L, int dtype) {
          V <= 1024 && L >= 1 && (dtype == 0 || dtype == 1);
 }
 
+// the GRU stack goes through the same tile: the same limits
+int pdrnn_gru_decode_supported(int B, int H, int E, int V, int L, int dtype) {
+  return pdrnn_lstm_decode_supported(B, H, E, V, L, dtype);
+}
+
+int pdrnn_gru_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype) {
+  return pdrnn_lstm_decode_beam_supported(G, W, H, E, V, L, dtype) && pdrnn_gru_decode_supported(G * W, H, E, V, L, dtype);
+}
+
 hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
   const PdrnnLstmDecodeStack& st = a->stack;
-  if (n_tokens < 1 || !pdrnn_lstm_decode_supported(st.B, st.H, st.E, st.V, st.L, st.dtype)) return hipErrorInvalidValue;
+  if (n_tokens < 1 || !pdrnn::stack_supported(st)) return hipErrorInvalidValue;
   if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
   return st.dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
 }
@@ -750,7 +803,7 @@ int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, i
 hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
   const PdrnnLstmDecodeStack& st = a->stack;
   if (n_tokens < 1 || !pdrnn_lstm_decode_beam_supported(a->G, a->W, st.H, st.E, st.V, st.L, st.dtype) ||
-      st.B != a->G * a->W)
+      st.B != a->G * a->W || !pdrnn::stack_supported(st))
     return hipErrorInvalidValue;
   if (a->stop < -1 || a->stop >= st.V || (a->hyp_lp != nullptr && a->lp == nullptr) || a->hyp == nullptr)
     return hipErrorInvalidValue;

@@ -2,6 +2,7 @@
 
     python -m pytorch_distributed_rnn_amd.lm_cli --hidden 1024 --layers 2 --seq-len 512 \\
         --batch-size 64 --max-steps 100 local
+    python -m pytorch_distributed_rnn_amd.lm_cli --cell gru --hidden 1024 --layers 2 --max-steps 100 local
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m pytorch_distributed_rnn_amd.lm_cli ... distributed
 
@@ -20,7 +21,8 @@ is global (strong scaling) unless ``--weak-scaling``.  ``--validation-fraction
 F`` holds the last F of the token stream out of training: every epoch then
 ends with its loss, bits per character and accuracy (``val_*`` in the
 history), and ``charlm-best.pt`` keeps the checkpoint with the lowest
-``val_loss``.  ``generate`` and ``evaluate`` rebuild the model from the
+``val_loss``.  ``--cell gru`` trains a GRU stack instead of the LSTM.
+``generate`` and ``evaluate`` rebuild the model, its cell included, from the
 checkpoint alone (only ``--dtype`` is read from the command line); ``generate``
 samples ``--samples`` continuations of the prompt -- or, with ``--beam-width
 W``, searches for the most likely ones with W beams and prints the ``--samples``
@@ -46,13 +48,15 @@ DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="char-LM LSTM training and generation")
+    p = argparse.ArgumentParser(description="char-LM LSTM / GRU training and generation")
     p.add_argument("--text", default=None)
     p.add_argument("--synthetic-tokens", type=int, default=4_000_000)
     p.add_argument("--vocab", type=int, default=256)
     p.add_argument("--embed", type=int, default=256)
     p.add_argument("--hidden", type=int, default=1024)
     p.add_argument("--layers", type=int, default=2)
+    p.add_argument("--cell", choices=("lstm", "gru"), default="lstm", help="the recurrent stack of a new model "
+                                                                            "(generate / evaluate: the checkpoint's)")
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--seq-len", type=int, default=512)
     p.add_argument("--batch-size", type=int, default=64)
@@ -244,7 +248,8 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     corpus, held = split_corpus(load_corpus(args), args.validation_fraction)
     _check_split(args, args.mode, corpus, held)
-    model = CharLM(corpus.vocab_size, args.embed, args.hidden, args.layers, args.dropout, DTYPES[args.dtype])
+    model = CharLM(corpus.vocab_size, args.embed, args.hidden, args.layers, args.dropout, DTYPES[args.dtype],
+                   cell=args.cell)
     device = torch.device(args.device) if args.device else None
     trainer = LMTrainer(model, corpus, args.batch_size, args.seq_len, args.learning_rate, device=device,
                         distributed=args.mode == "distributed", backend=args.backend,

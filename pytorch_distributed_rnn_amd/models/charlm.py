@@ -1,5 +1,5 @@
-"""Character-level LSTM language model (BASELINE config 4: 2-layer LSTM,
-hidden 1024, seq_len 512, DDP) and the stacked bidirectional LSTM encoder
+"""Character-level LSTM (or GRU) language model (BASELINE config 4: 2-layer
+LSTM, hidden 1024, seq_len 512, DDP) and the stacked bidirectional LSTM encoder
 (BASELINE config 5: hidden 4096, fp16).
 
 Neither model exists in the reference (no GRU / embedding /
@@ -23,21 +23,50 @@ from torch.nn import functional as F
 
 from ..ops.embedding import embedding
 from ..ops.gemm import linear
-from .rnn import LSTM
+from .rnn import GRU, LSTM
+
+
+def _map_state(f, state):
+    """``f`` of a state's tensor(s): (h, c) for the LSTM, h for the GRU, None as it is."""
+    if state is None or isinstance(state, Tensor):
+        return f(state) if state is not None else None
+    return tuple(f(x) for x in state)
+
+
+def _cat_states(states):
+    """Row groups' states joined along the batch."""
+    if isinstance(states[0], Tensor):
+        return torch.cat(states, 1)
+    return tuple(torch.cat(xs, 1) for xs in zip(*states))
 
 
 class CharLM(nn.Module):
+    """``cell``: "lstm" (the recurrent stack is ``self.lstm``, the state an
+    (h, c) pair) or "gru" (``self.gru``, the state the tensor h); ``self.rnn``
+    is whichever the model has."""
+
     def __init__(self, vocab_size: int = 256, embed_dim: int = 256, hidden_dim: int = 1024,
-                 num_layers: int = 2, dropout: float = 0.0, compute_dtype: torch.dtype = torch.bfloat16):
+                 num_layers: int = 2, dropout: float = 0.0, compute_dtype: torch.dtype = torch.bfloat16,
+                 cell: str = "lstm"):
         super().__init__()
+        if cell not in ("lstm", "gru"):
+            raise ValueError(f"cell must be 'lstm' or 'gru', not {cell!r}")
+        self.cell = cell
         self.vocab_size = vocab_size
         self.hidden_dim = hidden_dim
         self.num_layers = num_layers
         self.compute_dtype = compute_dtype
         self.embedding = nn.Embedding(vocab_size, embed_dim)
-        self.lstm = LSTM(embed_dim, hidden_dim, num_layers, batch_first=False, dropout=dropout)
+        if cell == "lstm":
+            self.lstm = LSTM(embed_dim, hidden_dim, num_layers, batch_first=False, dropout=dropout)
+        else:
+            self.gru = GRU(embed_dim, hidden_dim, num_layers, batch_first=False, dropout=dropout)
         self.fc = nn.Linear(hidden_dim, vocab_size)
-        self._state: Optional[Tuple[Tensor, Tensor]] = None
+        self._state = None  # the truncated-BPTT carry: (h, c), or the GRU's h
+
+    @property
+    def rnn(self):
+        return self.lstm if self.cell == "lstm" else self.gru
 
     def reset_hidden_state(self) -> None:
         """Start a new TBPTT stream (called at every epoch start)."""
@@ -46,8 +75,7 @@ class CharLM(nn.Module):
     def _cdt(self, device) -> torch.dtype:
         return self.compute_dtype if device.type == "cuda" else torch.float32
 
-    def forward(self, tokens: Tensor, state: Optional[Tuple[Tensor, Tensor]] = None,
-                carry: bool = False) -> Tensor:
+    def forward(self, tokens: Tensor, state=None, carry: bool = False) -> Tensor:
         """tokens [B, T] -> logits [T, B, V] (sequence-first, compute dtype).
 
         ``carry=True`` continues from (and updates) the detached state of the
@@ -56,9 +84,9 @@ class CharLM(nn.Module):
         x = embedding(tokens.t(), self.embedding.weight, out_dtype=cdt)      # [T, B, E]
         if state is None and carry:
             state = self._state
-        out, (hn, cn) = self.lstm(x, state)
+        out, state = self.rnn(x, state)
         if carry:
-            self._state = (hn.detach(), cn.detach())
+            self._state = _map_state(Tensor.detach, state)
         return linear(out, self.fc.weight, self.fc.bias)  # in-tree GEMM head (ops/gemm.py)
 
     def _step(self, tokens: Tensor, state):
@@ -76,7 +104,7 @@ class CharLM(nn.Module):
         model runs in eval mode and ``prompt[:, :-1]`` through ``_step`` from
         ``state``; the training mode and the truncated-BPTT carry are put back
         on the way out.  Yields (P, the first input tokens [B], the state after
-        the prefix, the compute dtype, whether the LSTM is one the decode
+        the prefix, the compute dtype, whether the stack is one the decode
         kernels know: biases, one direction, no projection)."""
         if prompt.dim() != 2 or prompt.shape[1] < 1:
             raise ValueError(f"{what}: prompt must be [B, P] with P >= 1")
@@ -91,21 +119,31 @@ class CharLM(nn.Module):
         try:
             if P > 1:
                 _, state = self._step(prompt[:, :-1], state)
-            plain = self.lstm.bias and not self.lstm.bidirectional and self.lstm.proj_size == 0
+            plain = self.rnn.bias and not self.rnn.bidirectional and getattr(self.rnn, "proj_size", 0) == 0
             yield P, prompt[:, -1], state, self._cdt(dev), plain
         finally:
             self._state = kept
             self.train(training)
 
+    def _entering(self, state, rows: slice):
+        """(h0, c0) of the decode ops for these rows of a state: a GRU's c0 is None."""
+        part = _map_state(lambda x: x[:, rows], state)
+        return (part, None) if self.cell == "gru" else (part if part is not None else (None, None))
+
+    def _leaving(self, h: Tensor, c: Tensor):
+        """The state out of the decode ops' (16-bit h, fp32 buffer): the GRU's is the buffer, h's fp32 master."""
+        return c if self.cell == "gru" else (h, c)
+
     @torch.no_grad()
     def generate(self, prompt: Tensor, num_tokens: int, temperature: float = 1.0, seed: int = 0,
-                 state: Optional[Tuple[Tensor, Tensor]] = None, forced: Optional[Tensor] = None,
+                 state=None, forced: Optional[Tensor] = None,
                  return_logits: bool = False, return_state: bool = False, top_k: int = 0, top_p: float = 1.0,
                  stop: Optional[int] = None, return_logprobs: bool = False, return_lengths: bool = False):
         """Sample ``num_tokens`` tokens after ``prompt`` [B, P] (P >= 1) ->
         tokens [B, num_tokens] int64 (, logits [B, num_tokens, V] fp32)
         (, log-probs [B, num_tokens] fp32) (, lengths [B] int64)
-        (, (h, c) [layers, B, H], c in fp32 on the fused path).
+        (, the state: (h, c) [layers, B, H], c in fp32 on the fused path; a
+        GRU's h, its fp32 master on the fused path).
 
         The rule is ops/decode.py's: ``token = argmax(logits / temperature +
         Gumbel noise)``, the noise a hash of (seed, row of the batch, position
@@ -148,24 +186,23 @@ class CharLM(nn.Module):
             B = first.shape[0]
             logprobs = None
             filt = dict(top_k=top_k, top_p=top_p, return_logprobs=return_logprobs)
-            if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev):
+            if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev, self.cell):
                 outs = []
                 for b0 in range(0, B, dec.MAX_STREAMS):
                     rows = slice(b0, min(b0 + dec.MAX_STREAMS, B))
                     outs.append(dec.decode(
-                        self.embedding.weight, self.lstm._weights(), self.fc.weight, self.fc.bias, cdt,
-                        state[0][:, rows] if state is not None else None, state[1][:, rows] if state is not None else None,
-                        first[rows], N, temperature=temperature, seed=seed, stream0=b0, pos0=P,
-                        forced=forced[rows] if forced is not None else None, return_logits=return_logits, **filt))
+                        self.embedding.weight, self.rnn._weights(), self.fc.weight, self.fc.bias, cdt,
+                        *self._entering(state, rows), first[rows], N, temperature=temperature, seed=seed, stream0=b0,
+                        pos0=P, forced=forced[rows] if forced is not None else None, return_logits=return_logits,
+                        cell=self.cell, **filt))
                 if len(outs) == 1:
-                    tokens, logits, h, c = outs[0][:4]
+                    tokens, logits = outs[0][:2]
                     logprobs = outs[0][4] if return_logprobs else None
                 else:
                     tokens = torch.cat([o[0] for o in outs], 0)
                     logits = torch.cat([o[1] for o in outs], 0) if return_logits else None
-                    h, c = torch.cat([o[2] for o in outs], 1), torch.cat([o[3] for o in outs], 1)
                     logprobs = torch.cat([o[4] for o in outs], 0) if return_logprobs else None
-                state = (h, c)
+                state = _cat_states([self._leaving(o[2], o[3]) for o in outs])
             else:
                 if N > 0:
                     _ext.fallback(f"char-LM decode (B={B}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
@@ -188,13 +225,13 @@ class CharLM(nn.Module):
 
     @torch.no_grad()
     def beam_search(self, prompt: Tensor, num_tokens: int, beam_width: int, stop: Optional[int] = None,
-                    length_penalty: float = 0.0, state: Optional[Tuple[Tensor, Tensor]] = None,
+                    length_penalty: float = 0.0, state=None,
                     return_logprobs: bool = False, return_state: bool = False):
         """The ``beam_width`` most likely continuations of ``prompt`` [B, P]
         (P >= 1) found by beam search -> tokens [B, W, num_tokens] int64 best
         first, scores [B, W] fp32, lengths [B, W] int64 (, per-token log-probs
-        [B, W, num_tokens] fp32 along each hypothesis) (, (h, c) [layers,
-        B * W, H], row b * W + i hypothesis i's).
+        [B, W, num_tokens] fp32 along each hypothesis) (, the state as in
+        ``generate``, [layers, B * W, H], row b * W + i hypothesis i's).
 
         The rule is ops/decode.py's: a hypothesis's score is the sum of its
         tokens' log-probs (softmax of the fp32 logits); ties keep the lower
@@ -222,40 +259,39 @@ class CharLM(nn.Module):
         with self._decoding("beam_search", prompt, state) as (_, first, state, cdt, plain):
             B = first.shape[0]
             per = dec.MAX_STREAMS // W
-            if plain and dec.beam_supported(min(B, per), W, H, E, V, L, cdt, dev):
+            if plain and dec.beam_supported(min(B, per), W, H, E, V, L, cdt, dev, self.cell):
                 outs = []
                 for b0 in range(0, B, per):
                     rows = slice(b0, min(b0 + per, B))
-                    outs.append(dec.beam_decode(
-                        self.embedding.weight, self.lstm._weights(), self.fc.weight, self.fc.bias, cdt,
-                        state[0][:, rows] if state is not None else None, state[1][:, rows] if state is not None else None,
-                        first[rows], N, W, stop=stop, return_logprobs=return_logprobs))
+                    o = dec.beam_decode(
+                        self.embedding.weight, self.rnn._weights(), self.fc.weight, self.fc.bias, cdt,
+                        *self._entering(state, rows), first[rows], N, W, stop=stop, return_logprobs=return_logprobs,
+                        cell=self.cell)
+                    outs.append(o[:3] + (self._leaving(o[3], o[4]),))
             else:
                 _ext.fallback(f"char-LM beam search (B={B}, W={W}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
-                o = dec.beam_reference(self._step, state, first, N, W, stop=stop, return_logprobs=return_logprobs)
-                outs = [o[:3] + tuple(o[3])]
+                outs = [dec.beam_reference(self._step, state, first, N, W, stop=stop, return_logprobs=return_logprobs)]
             hyp, scores = torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0).float()
             logprobs = torch.cat([o[2] for o in outs], 0).float() if return_logprobs else None
-            h, c = torch.cat([o[3] for o in outs], 1), torch.cat([o[4] for o in outs], 1)
+            state = _cat_states([o[3] for o in outs])
         order, lengths, scores = dec.beam_finish(hyp, scores, stop, length_penalty)
         if length_penalty:
             hyp = hyp.gather(1, order[:, :, None].expand_as(hyp))
             if logprobs is not None:
                 logprobs = logprobs.gather(1, order[:, :, None].expand_as(logprobs))
             rows = (order + torch.arange(B, device=dev)[:, None] * W).reshape(-1)
-            h, c = h.index_select(1, rows), c.index_select(1, rows)
+            state = _map_state(lambda x: x.index_select(1, rows), state)
         return ((hyp, scores, lengths) + ((logprobs,) if return_logprobs else ())
-                + (((h, c),) if return_state else ()))
+                + ((state,) if return_state else ()))
 
     @torch.no_grad()
-    def score(self, inputs: Tensor, targets: Tensor, state: Optional[Tuple[Tensor, Tensor]] = None,
-              return_state: bool = False, ignore_index: int = -100, accum: Optional[Tensor] = None):
+    def score(self, inputs: Tensor, targets: Tensor, state=None, return_state: bool = False, ignore_index: int = -100, accum: Optional[Tensor] = None):
         """Per-token log-probabilities of ``targets`` [B, T] after ``inputs``
-        [B, T] -> (logprob [B, T] fp32, pred [B, T] int32) (, (h, c) [layers,
-        B, H]); ``logprob`` is 0 where the target is ``ignore_index``, ``pred``
+        [B, T] -> (logprob [B, T] fp32, pred [B, T] int32) (, the state [layers,
+        B, H]: (h, c), or a GRU's h); ``logprob`` is 0 where the target is ``ignore_index``, ``pred``
         the argmax of the position's logits (the lowest index on ties).
 
-        The embedding and the LSTM stack run as in ``forward`` from ``state``
+        The embedding and the recurrent stack run as in ``forward`` from ``state``
         (zeros when None); the vocabulary head, the log-softmax and the NLL are
         one kernel on the top layer's output in place (ops/head_nll.py), with
         the logits in fp32 from the product to the loss -- ``forward`` would
@@ -273,29 +309,33 @@ class CharLM(nn.Module):
         self.eval()
         try:
             x = embedding(inputs.t(), self.embedding.weight, out_dtype=self._cdt(dev))  # [T, B, E]
-            out, (hn, cn) = self.lstm(x, state)                                          # [T, B, H]
+            out, state = self.rnn(x, state)                                              # [T, B, H]
             row_nll, pred, _ = head_nll(out, self.fc.weight, self.fc.bias, targets.t().contiguous(), ignore_index, accum)
         finally:
             self.train(training)
         logprob = -row_nll.view(T, B).t()
         pred = pred.view(T, B).t()
-        return (logprob, pred, (hn, cn)) if return_state else (logprob, pred)
+        return (logprob, pred, state) if return_state else (logprob, pred)
 
 
 def charlm_from_state_dict(state, compute_dtype: torch.dtype = torch.bfloat16) -> CharLM:
     """A ``CharLM`` with the hyper-parameters a checkpoint's ``model_state``
     implies, its parameters loaded: vocabulary and embedding width from
-    ``embedding.weight``, the hidden size from ``lstm.weight_hh_l0``, the
-    layers from the key count; DDP's ``module.`` prefix is accepted."""
+    ``embedding.weight``, the cell from which of ``lstm.weight_hh_l0`` and
+    ``gru.weight_hh_l0`` is there, the hidden size from it, the layers from
+    the key count; DDP's ``module.`` prefix is accepted."""
     from ..train.checkpoint import adapt_state_dict_keys
     plain = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
-    for k in ("embedding.weight", "lstm.weight_hh_l0", "fc.weight"):
+    cell = "gru" if "gru.weight_hh_l0" in plain else "lstm"
+    for k in ("embedding.weight", f"{cell}.weight_hh_l0", "fc.weight"):
         if k not in plain:
             raise KeyError(f"not a char-LM state: {k} missing")
     vocab, embed = (int(n) for n in plain["embedding.weight"].shape)
-    hidden = int(plain["lstm.weight_hh_l0"].shape[1])
-    layers = sum(1 for k in plain if k.startswith("lstm.weight_hh_l") and not k.endswith("_reverse"))
-    model = CharLM(vocab, embed, hidden, layers, compute_dtype=compute_dtype)
+    rows, hidden = (int(n) for n in plain[f"{cell}.weight_hh_l0"].shape)
+    if rows != (3 if cell == "gru" else 4) * hidden:
+        raise ValueError(f"not a char-LM state: {cell}.weight_hh_l0 is [{rows}, {hidden}]")
+    layers = sum(1 for k in plain if k.startswith(f"{cell}.weight_hh_l") and not k.endswith("_reverse"))
+    model = CharLM(vocab, embed, hidden, layers, compute_dtype=compute_dtype, cell=cell)
     model.load_state_dict(adapt_state_dict_keys(dict(state), model))
     return model
 

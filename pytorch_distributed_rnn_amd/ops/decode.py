@@ -59,6 +59,13 @@ j`` is beam j of group g.
 
 ``length_penalty`` a re-ranks the final W, stably, by cum / length^a
 (``beam_finish``): at the end only, on the device.
+
+Cells.  ``cell="gru"`` runs the same ops on a GRU stack (nn.GRU's weights,
+gates r, z, n).  The fp32 buffer that holds c for the LSTM then holds the fp32
+master of h, updated in place by ``h_t = n + z (h_{t-1} - n)``; the 16-bit h is
+its rounding and is what the products read.  A GRU's state is that one tensor:
+``decode`` and ``beam_decode`` return the master in c's place, and feeding it
+back continues a run bit for bit.
 """
 from __future__ import annotations
 
@@ -71,8 +78,10 @@ from .. import _ext
 from . import shadow as _sh
 from .lstm_large import _DTYPE_CODE, _bias_cat, shadow
 
+CELLS = ("lstm", "gru")
+
 __all__ = ["gumbel_noise", "keep_threshold", "token_logprobs", "check_filters", "sample", "supported", "alloc_buffers",
-           "decode", "reference", "MAX_STREAMS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
+           "decode", "reference", "MAX_STREAMS", "CELLS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
            "stop_lengths", "beam_finish", "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
 
 MAX_STREAMS = 16  # streams per launch: the 16-wide side of the MFMA tile
@@ -208,9 +217,15 @@ def _covered(op: str, dtype: torch.dtype, device, *shape: int) -> bool:
     return bool(getattr(mod, op + "_supported")(*shape, _DTYPE_CODE[dtype]))
 
 
-def supported(B: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
-    """The fused decode kernels run this shape on ``device``."""
-    return _covered("lstm_decode", dtype, device, B, H, E, V, L)
+def supported(B: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device, cell: str = "lstm") -> bool:
+    """The fused decode kernels run this shape of a ``cell`` stack on ``device``."""
+    return _covered(_op(cell, "decode"), dtype, device, B, H, E, V, L)
+
+
+def _op(cell: str, what: str) -> str:
+    if cell not in CELLS:
+        raise ValueError(f"cell must be one of {CELLS}, not {cell!r}")
+    return f"{cell}_{what}"
 
 
 def _stack_dims(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor) -> tuple:
@@ -218,14 +233,45 @@ def _stack_dims(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor) -> 
     return (emb_w.device, _ext.native(emb_w.device), *emb_w.shape, fc_w.shape[1], len(lstm_weights) // 4)
 
 
-def _stack_operands(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt) -> tuple:
-    """Both ops' leading arguments: emb, w_ih / w_hh / b_ih + b_hh per layer, fc_w, fc_b; the weights in
-    ``cdt`` from the shadow registry, the biases in fp32."""
+def _stack_operands(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt,
+                    cell: str = "lstm") -> tuple:
+    """Both ops' leading arguments: emb, w_ih / w_hh / the folded bias per layer, fc_w, fc_b; the weights in
+    ``cdt`` from the shadow registry, the biases in fp32.  The LSTM's matrices are gate-interleaved copies; the
+    GRU's are ops/gru_large.py's zero-padded interleaved stacks [r | z | n_x | 0], [r | z | 0 | n_h] and its
+    folded bias [b_ir + b_hr, b_iz + b_hz, b_in, b_hn]."""
     H, L = fc_w.shape[1], len(lstm_weights) // 4
-    w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
-    w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
-    bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, emb_w.device) for l in range(L)]
+    if cell == "gru":
+        from .gru_large import _gru_shadows  # (the training kernels' own stacks: nothing new to keep fresh)
+        sh = [_gru_shadows(lstm_weights[4 * l:4 * l + 4], 1, H, lstm_weights[4 * l].shape[1], cdt, emb_w.device) for l in range(L)]
+        w_ih, w_hh, bias = [x[1] for x in sh], [x[3][0] for x in sh], [x[5] for x in sh]
+    else:
+        w_ih = [shadow(lstm_weights[4 * l], "i", cdt, H) for l in range(L)]
+        w_hh = [shadow(lstm_weights[4 * l + 1], "i", cdt, H) for l in range(L)]
+        bias = [_bias_cat(list(lstm_weights[4 * l:4 * l + 4]), 1, H, emb_w.device) for l in range(L)]
     return (_sh.cast(emb_w, cdt), w_ih, w_hh, bias, _sh.cast(fc_w, cdt), fc_b.detach().float() if fc_b is not None else None)
+
+
+def _init_state(cell: str, h: Tensor, c: Tensor, h0: Optional[Tensor], c0: Optional[Tensor], beams: int = 0) -> None:
+    """The entering state into ``h[0]`` and ``c``; ``beams`` W > 0: each of the G given rows W times.  LSTM: h0
+    and c0.  GRU: h0 of any float dtype widened exactly into the fp32 master (``c``), its rounding into ``h[0]``."""
+    if cell != "lstm" and c0 is not None:
+        raise ValueError("a GRU's state is h alone: c0 must be None")
+    L, S, H = c.shape
+
+    def put(dst, src):
+        if src is None:
+            dst.zero_()
+        elif beams:
+            dst.view(L, S // beams, beams, H).copy_(src[:, :, None, :])
+        else:
+            dst.copy_(src)
+
+    if cell != "lstm":
+        put(c, h0)
+        h[0].copy_(c)
+    else:
+        put(h[0], h0)
+        put(c, c0)
 
 
 def _alloc_stack(L: int, B: int, H: int, V: int, N: int, cdt, device, return_logits: bool) -> Dict[str, Optional[Tensor]]:
@@ -253,7 +299,7 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
            h0: Optional[Tensor], c0: Optional[Tensor], first: Tensor, num_tokens: int, *, temperature: float = 1.0,
            seed: int = 0, stream0: int = 0, pos0: int = 0, forced: Optional[Tensor] = None,
            return_logits: bool = False, bufs: Optional[Dict[str, Optional[Tensor]]] = None, top_k: int = 0,
-           top_p: float = 1.0, return_threshold: bool = False, return_logprobs: bool = False):
+           top_p: float = 1.0, return_threshold: bool = False, return_logprobs: bool = False, cell: str = "lstm"):
     """``num_tokens`` positions on the fused kernels for B <= 16 streams.
 
     emb_w [V, E], lstm_weights (w_ih, w_hh, b_ih, b_hh per layer), fc_w [V, H],
@@ -265,27 +311,29 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
     rule above, found inside the layer-0 launch.  Returns (tokens [B, N],
     logits [B, N, V] or None, h [L, B, H] in ``cdt``, c [L, B, H] fp32), then
     the thresholds [B, N] and the tokens' log-probabilities [B, N] (fp32), each
-    only when asked for: views of the buffers."""
+    only when asked for: views of the buffers.  ``cell="gru"``: nn.GRU's
+    weights, c0 None, h0 of any float dtype; the fourth result is h's fp32
+    master, of which the third is the rounding (Cells, above)."""
     dev, mod, V, E, H, L = _stack_dims(emb_w, lstm_weights, fc_w)
     B, N = first.shape[0], int(num_tokens)
-    if mod is None or not supported(B, H, E, V, L, cdt, dev):
-        raise RuntimeError(f"lstm_decode does not cover B={B} H={H} E={E} V={V} L={L} {cdt} on {dev}")
+    if mod is None or not supported(B, H, E, V, L, cdt, dev, cell):
+        raise RuntimeError(f"{cell}_decode does not cover B={B} H={H} E={E} V={V} L={L} {cdt} on {dev}")
     if N < 1:
         raise ValueError("num_tokens must be at least 1")
     check_filters(top_k, top_p)
     with torch.no_grad():
-        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt)
+        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt, cell)
         if bufs is None:
             bufs = alloc_buffers(L, B, H, V, N, cdt, dev, return_logits, return_threshold, return_logprobs)
         h, c = bufs["h"], bufs["c"]
-        h[0].copy_(h0) if h0 is not None else h[0].zero_()
-        c.copy_(c0) if c0 is not None else c.zero_()
-        mod.lstm_decode(*stack, h, c, bufs["scratch"], first.to(dev, torch.int64).contiguous(),
-                        forced.to(dev, torch.int64).contiguous() if forced is not None else None, bufs["tokens"],
-                        bufs["logits"] if return_logits else None, float(temperature), int(seed) & _M32,
-                        int(stream0) & _M32, int(pos0) & _M32, top_k=min(int(top_k), V), top_p=float(top_p),
-                        threshold=bufs["threshold"] if return_threshold else None,
-                        logprobs=bufs["logprobs"] if return_logprobs else None)
+        _init_state(cell, h, c, h0, c0)
+        getattr(mod, _op(cell, "decode"))(
+            *stack, h, c, bufs["scratch"], first.to(dev, torch.int64).contiguous(),
+            forced.to(dev, torch.int64).contiguous() if forced is not None else None, bufs["tokens"],
+            bufs["logits"] if return_logits else None, float(temperature), int(seed) & _M32,
+            int(stream0) & _M32, int(pos0) & _M32, top_k=min(int(top_k), V), top_p=float(top_p),
+            threshold=bufs["threshold"] if return_threshold else None,
+            logprobs=bufs["logprobs"] if return_logprobs else None)
     out = (bufs["tokens"], bufs["logits"] if return_logits else None, h[N & 1], c)
     return out + ((bufs["threshold"],) if return_threshold else ()) + ((bufs["logprobs"],) if return_logprobs else ())
 
@@ -381,9 +429,10 @@ def beam_finish(hyp: Tensor, scores: Tensor, stop: Optional[int], length_penalty
     return order, lengths, scores
 
 
-def beam_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device) -> bool:
-    """The fused decode kernels run a beam search of G groups of W beams."""
-    return _covered("lstm_decode_beam", dtype, device, G, W, H, E, V, L)
+def beam_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device,
+                   cell: str = "lstm") -> bool:
+    """The fused decode kernels run a beam search of G groups of W beams on a ``cell`` stack."""
+    return _covered(_op(cell, "decode_beam"), dtype, device, G, W, H, E, V, L)
 
 
 def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torch.dtype, device,
@@ -409,7 +458,7 @@ def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torc
 def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt: torch.dtype,
                 h0: Optional[Tensor], c0: Optional[Tensor], first: Tensor, num_tokens: int, width: int, *,
                 stop: Optional[int] = None, return_logits: bool = False, return_logprobs: bool = False,
-                bufs: Optional[Dict[str, Optional[Tensor]]] = None):
+                bufs: Optional[Dict[str, Optional[Tensor]]] = None, cell: str = "lstm"):
     """Beam search over ``num_tokens`` positions on the fused kernels: G =
     len(first) prompts, ``width`` beams each, G * width <= 16.
 
@@ -419,26 +468,26 @@ def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_
     (``alloc_beam_buffers``); they keep every selection's record.  Returns
     (hyp [G, W, N] int64 in rank order, scores [G, W] fp32, hyp_lp [G, W, N] or
     None, h [L, G * W, H] in ``cdt``, c [L, G * W, H] fp32): the state entering
-    position N of each hypothesis, the last token not fed, as in ``decode``."""
+    position N of each hypothesis, the last token not fed, as in ``decode``
+    (``cell="gru"``: c0 None, and the last result is h's fp32 master)."""
     dev, mod, V, E, H, L = _stack_dims(emb_w, lstm_weights, fc_w)
     G, N, W = first.shape[0], int(num_tokens), int(width)
     check_beam(width, stop, V, N, G)
-    if mod is None or not beam_supported(G, W, H, E, V, L, cdt, dev):
-        raise RuntimeError(f"lstm_decode_beam does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
+    if mod is None or not beam_supported(G, W, H, E, V, L, cdt, dev, cell):
+        raise RuntimeError(f"{cell}_decode_beam does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
     with torch.no_grad():
-        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt)
+        stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt, cell)
         if bufs is None:
             bufs = alloc_beam_buffers(L, G, W, H, V, N, cdt, dev, return_logits, return_logprobs)
         h, c = bufs["h"], bufs["c"]
-        h[0].view(L, G, W, H).copy_(h0[:, :, None, :]) if h0 is not None else h[0].zero_()
-        c.view(L, G, W, H).copy_(c0[:, :, None, :]) if c0 is not None else c.zero_()
+        _init_state(cell, h, c, h0, c0, beams=W)
         bufs["cum"][0].copy_(beam_start(G, W, dev))
         bufs["done"][0].zero_()
-        mod.lstm_decode_beam(*stack, h, c, bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(),
-                             bufs["cum"], bufs["done"], bufs["tokens"], bufs["parents"],
-                             bufs["lp"] if return_logprobs else None, bufs["logits"] if return_logits else None,
-                             bufs["hyp"], bufs["hyp_lp"] if return_logprobs else None, G, W,
-                             -1 if stop is None else int(stop))
+        getattr(mod, _op(cell, "decode_beam"))(
+            *stack, h, c, bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(),
+            bufs["cum"], bufs["done"], bufs["tokens"], bufs["parents"],
+            bufs["lp"] if return_logprobs else None, bufs["logits"] if return_logits else None,
+            bufs["hyp"], bufs["hyp_lp"] if return_logprobs else None, G, W, -1 if stop is None else int(stop))
         last = bufs["parents"][:, N - 1].to(torch.int64)
         hn, cn = h[N & 1].index_select(1, last), c.index_select(1, last)
     return (bufs["hyp"].view(G, W, N), bufs["cum"][N].view(G, W),
@@ -450,7 +499,7 @@ def beam_reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], stat
                    return_trace: bool = False, dtype: torch.dtype = torch.float32):
     """The same search as a host loop: ``step(tokens [S, 1], state) -> (logits
     [S, V], state)`` once per position on S = G * width streams, ``state`` a
-    tuple of [layers, streams, H] tensors (or None), then ``beam_select`` in
+    [layers, streams, H] tensor or a tuple of them (or None), then ``beam_select`` in
     ``dtype`` and a gather of the state by the parents.  Returns (hyp
     [G, W, N], scores [G, W], hyp_lp [G, W, N] or None, state) as
     ``beam_decode`` does, then, asked for, the trace: a dict of ``tokens``,
@@ -460,9 +509,13 @@ def beam_reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], stat
     dev = first.device
     S = G * W
     src = torch.arange(G, device=dev).repeat_interleave(W)
+
+    def rows(state, idx):
+        return state.index_select(1, idx) if isinstance(state, Tensor) else tuple(x.index_select(1, idx) for x in state)
+
     with torch.no_grad():
         if state is not None:
-            state = tuple(x.index_select(1, src) for x in state)
+            state = rows(state, src)
         tok = first[src]
         cum, done = beam_start(G, W, dev, dtype), torch.zeros(S, dtype=torch.bool, device=dev)
         toks, pars, lps, cums, dones, lgs = [], [], [], [cum], [done], []
@@ -475,8 +528,8 @@ def beam_reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], stat
             if return_trace:
                 lgs.append(logits)
             if p + 1 < N:
-                state = tuple(x.index_select(1, parent) for x in state)
-        state = tuple(x.index_select(1, parent) for x in state)
+                state = rows(state, parent)
+        state = rows(state, parent)
         tokens, parents, lp = torch.stack(toks, 1), torch.stack(pars, 1), torch.stack(lps, 1)
         hyp, hyp_lp = beam_backtrace(tokens, parents, lp if return_logprobs else None)
     out = (hyp.view(G, W, N), cum.view(G, W), hyp_lp.view(G, W, N) if return_logprobs else None, state)
