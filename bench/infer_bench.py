@@ -12,8 +12,12 @@ evaluation).  Every timing is ``--repeats`` evaluations back to back and ends
 in a device synchronise (for batch 1 each call synchronises: it is a latency).
 Prints one JSON line per (cell, batch size): the pairs in ms per evaluation,
 both medians and ranges, and whether the fused path won every pair.
+``--bidirectional`` runs the bidirectional LSTM with one and with two layers
+instead (kernels/lstm_bidir_infer.hip against the per-direction launches of
+``model.forward``).
 
     python bench/infer_bench.py [--pairs 5] [--repeats 5] [--warmup 2] [--batches 1440 691 180 1] [--out FILE]
+                                [--bidirectional]
 """
 from __future__ import annotations
 
@@ -53,6 +57,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batches", type=int, nargs="+", default=[1440, 691, 180, 1],
                     help="batch sizes; 1 times single calls on one sequence, any other size whole evaluations")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="the bidirectional LSTM with 1 and 2 layers instead of the 2-layer LSTM and GRU")
     args = ap.parse_args(argv)
 
     from pytorch_distributed_rnn_amd.data.motion import synthetic_motion
@@ -66,9 +72,10 @@ def main(argv=None) -> int:
     train, _, _ = synthetic_motion(n_train=args.sequences, n_validation=2, n_test=2, seed=0)
     fmt = TrainingMessageFormatter(1)
     lines = []
-    for cell in ("lstm", "gru"):
+    configs = [("lstm", 1, True), ("lstm", 2, True)] if args.bidirectional else [("lstm", 2, False), ("gru", 2, False)]
+    for cell, layers, bidir in configs:
         torch.manual_seed(0)
-        model = MotionModel(9, 32, 2, 6, cell=cell)
+        model = MotionModel(9, 32, layers, 6, cell=cell, bidirectional=bidir)
         trainer = Trainer(model, train, batch_size=1440, learning_rate=2.5e-3, device=dev, warmup=False)
         assert fused_eval.supported(trainer.model, dev), "the fused inference path does not serve the flagship model"
         one = train.features[:1].to(dev).contiguous()
@@ -100,7 +107,7 @@ def main(argv=None) -> int:
             torch.cuda.synchronize()
             pairs = [(_timed(run[False], args.repeats), _timed(run[True], args.repeats)) for _ in range(args.pairs)]
             old, new = [p[0] for p in pairs], [p[1] for p in pairs]
-            rec = {"cell": cell, "batch": bs, "what": what,
+            rec = {"cell": cell, "layers": layers, "bidirectional": bidir, "batch": bs, "what": what,
                    "pairs_ms": [[round(a, 4), round(b, 4)] for a, b in pairs],
                    "forward_ms": {"median": round(statistics.median(old), 4), "min": round(min(old), 4),
                                   "max": round(max(old), 4)},

@@ -111,7 +111,11 @@ def _run(cmd, verbose):
 # (mode 4) keep their MFMA accumulators in VGPRs -- in AGPRs they would be
 # allocated beside the BPTT waves' VGPRs (one kernel, one register budget)
 # and the workgroup would drop to one wave per SIMD.
-_FILE_FLAGS = {"lstm_sw": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+# lstm_bidir_infer: plain v_fma_f32 products, the packed fp32 operations off.
+_FILE_FLAGS = {
+    "lstm_sw": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "lstm_bidir_infer": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def build(verbose: bool = False, clean: bool = False, jobs: int | None = None) -> Path:

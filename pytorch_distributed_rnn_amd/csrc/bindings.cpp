@@ -458,6 +458,98 @@ py::tuple lstm_head_infer(const Tensor& x, const optional<Tensor>& idx, const op
   return py::make_tuple(logits, pred, opt_t(seq_stats), opt_t(hn), opt_t(cn));
 }
 
+// Bidirectional motion inference in one launch (pdrnn_lstm_bidir_infer).  w:
+// the stack in nn.LSTM(bidirectional=True) parameter order, per layer
+// (w_ih, w_hh, b_ih, b_hh) of the forward then of the reverse direction;
+// head_w is [C, 2H].  x, idx and labels as lstm_head_infer.  ns < 0 asks the
+// plan.  Returns (logits [B, C], pred [B], seq_stats [B, 3] or None), written
+// into logits_out / pred_out / stats_out where given (contiguous, those shapes).
+py::tuple lstm_bidir_head_infer(const Tensor& x, const optional<Tensor>& idx, const optional<Tensor>& labels,
+                                const std::vector<Tensor>& w, const Tensor& head_w, const optional<Tensor>& head_b,
+                                int64_t H, int64_t NL, int64_t ns, const optional<Tensor>& logits_out,
+                                const optional<Tensor>& pred_out, const optional<Tensor>& stats_out) {
+  CHECK_HIP_TENSOR(x);
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "x must be float32");
+  TORCH_CHECK(x.dim() == 3 && x.stride(2) == 1, "x must be [N, T, I] with contiguous rows");
+  const c10::DeviceGuard guard(x.device());
+  const int64_t I = x.size(2);
+  TORCH_CHECK(pdrnn_lstm_bidir_infer_ok((int)H, (int)I, (int)NL, 0) == 1,
+              "bidirectional motion inference serves H = 32, 1 <= I <= 12, 1 or 2 layers; got H=", H, ", I=", I,
+              ", layers=", NL);
+  TORCH_CHECK((int64_t)w.size() == 8 * NL, "expected (w_ih, w_hh, b_ih, b_hh) per layer and direction, with biases");
+  PdrnnLstmBidirInferArgs a{};
+  for (int64_t l = 0; l < NL; ++l)
+    for (int64_t d = 0; d < 2; ++d) {
+      const int64_t Iin = l == 0 ? I : 2 * H;
+      const int64_t sizes[4][2] = {{4 * H, Iin}, {4 * H, H}, {4 * H, 1}, {4 * H, 1}};
+      const float* p[4];
+      for (int k = 0; k < 4; ++k) {
+        const Tensor& t = w[(l * 2 + d) * 4 + k];
+        TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == x.device() && t.scalar_type() == at::kFloat &&
+                    t.is_contiguous() && t.numel() == sizes[k][0] * sizes[k][1] && t.size(0) == 4 * H,
+                    "bidirectional stack: parameter ", k, " of layer ", l, " direction ", d, " must be contiguous fp32 ",
+                    "with ", sizes[k][0], " x ", sizes[k][1], " elements");
+        p[k] = t.data_ptr<float>();
+      }
+      a.w_ih[l][d] = p[0]; a.w_hh[l][d] = p[1]; a.b_ih[l][d] = p[2]; a.b_hh[l][d] = p[3];
+    }
+  const bool gathered = idx.has_value() && idx->defined();
+  if (gathered)
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->is_contiguous() && idx->device() == x.device(),
+                "idx must be a contiguous int64 tensor on x's device");
+  TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == 2 * H && head_w.is_contiguous() &&
+              head_w.scalar_type() == at::kFloat && head_w.device() == x.device(), "head weight must be fp32 [C, 2H]");
+  const int64_t C = head_w.size(0);
+  TORCH_CHECK(C >= 1 && C <= 16, "motion inference serves 1..16 classes, got ", C);
+  const bool has_hb = head_b.has_value() && head_b->defined();
+  if (has_hb)
+    TORCH_CHECK(head_b->numel() == C && head_b->is_contiguous() && head_b->scalar_type() == at::kFloat &&
+                head_b->device() == x.device(), "head bias [C]");
+  const bool has_lab = labels.has_value() && labels->defined();
+  if (has_lab)
+    TORCH_CHECK(labels->scalar_type() == at::kLong && labels->is_contiguous() && labels->device() == x.device() &&
+                labels->numel() >= x.size(0), "labels must be int64, one per row of x");
+  a.x = x.data_ptr<float>();
+  a.idx = gathered ? idx->data_ptr<int64_t>() : nullptr;
+  a.x_sb = x.stride(0); a.x_st = x.stride(1);
+  a.B = (int)(gathered ? idx->numel() : x.size(0)); a.T = (int)x.size(1); a.I = (int)I;
+  const int64_t B = a.B, T = a.T;
+  TORCH_CHECK(B > 0 && T > 0, "motion inference: empty batch");
+  int nseq = (int)ns;
+  if (ns < 0) {
+    nseq = pdrnn_lstm_bidir_infer_plan((int)NL, (int)B, (int)T, nullptr);
+    TORCH_CHECK(nseq > 0, "bidirectional motion inference: T=", T, " with ", NL, " layer(s) exceeds 64 KiB of LDS");
+  }
+  auto opts = x.options().dtype(at::kFloat);
+  auto out_or = [&](const optional<Tensor>& given, std::vector<int64_t> shape, at::ScalarType dt) {
+    if (!given.has_value() || !given->defined()) return at::empty(shape, opts.dtype(dt));
+    TORCH_CHECK(given->device() == x.device() && given->scalar_type() == dt && given->is_contiguous() &&
+                given->sizes().vec() == shape, "bidirectional motion inference: a given output has the wrong "
+                "device, dtype, shape or strides");
+    return *given;
+  };
+  Tensor logits = out_or(logits_out, {B, C}, at::kFloat), pred = out_or(pred_out, {B}, at::kLong);
+  Tensor seq_stats;
+  a.head_w = head_w.data_ptr<float>();
+  a.head_b = has_hb ? head_b->data_ptr<float>() : nullptr;
+  a.logits = logits.data_ptr<float>();
+  a.pred = pred.data_ptr<int64_t>();
+  if (has_lab) {
+    seq_stats = out_or(stats_out, {B, 3}, at::kFloat);
+    a.labels = labels->data_ptr<int64_t>();
+    a.seq_stats = seq_stats.data_ptr<float>();
+  }
+  a.inv_batch = 1.f / (float)B;
+  a.C = (int)C; a.NL = (int)NL;
+  const hipError_t err = pdrnn_lstm_bidir_infer(&a, nseq, cur_stream());
+  TORCH_CHECK(err != hipErrorInvalidValue && err != hipErrorInvalidConfiguration, "bidirectional motion inference: ",
+              nseq, " sequence(s) per workgroup do not run layers=", NL, ", T=", T, " (1..4 sequences within 64 KiB of LDS)");
+  HIP_LAUNCH_CHECK(err);
+  py::object stats = py::none();
+  if (seq_stats.defined()) stats = py::cast(seq_stats);
+  return py::make_tuple(logits, pred, stats);
+}
+
 // Returns {dparams_flat[P] (nn.LSTM parameter order), dx, dh0, dc0}.
 std::vector<Tensor> lstm_small_bwd(const Tensor& x, const optional<Tensor>& idx,
                                    const std::vector<optional<Tensor>>& w_in, const optional<Tensor>& h0,
@@ -2144,6 +2236,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return d;
   }, "the wave map of lstm_head_infer for B sequences of T steps and its sequences per workgroup: the forward "
      "thresholds of lstm_sw_plan without its batch limit.  cus: for a device of that many compute units",
+        py::arg("NL"), py::arg("B"), py::arg("T"), py::arg("cus") = py::none());
+  m.def("lstm_bidir_head_infer", &lstm_bidir_head_infer,
+        "bidirectional motion inference in one launch -> (logits [B,C], pred [B], seq_stats [B,3] or None)",
+        py::arg("x"), py::arg("idx"), py::arg("labels"), py::arg("w"), py::arg("head_w"), py::arg("head_b"),
+        py::arg("H"), py::arg("NL"), py::arg("ns") = -1, py::arg("logits_out") = py::none(),
+        py::arg("pred_out") = py::none(), py::arg("stats_out") = py::none());
+  m.def("lstm_bidir_infer_ok", [](int64_t H, int64_t I, int64_t NL, int64_t cell) {
+    return pdrnn_lstm_bidir_infer_ok((int)H, (int)I, (int)NL, (int)cell) != 0;
+  }, py::arg("H"), py::arg("I"), py::arg("NL"), py::arg("cell") = 0);
+  m.def("lstm_bidir_infer_plan", [](int64_t NL, int64_t B, int64_t T, const optional<int64_t>& cus) {
+    int lds = 0;
+    const int ns = cus.has_value() ? pdrnn_lstm_bidir_infer_plan_cus((int)NL, (int)B, (int)T, (int)*cus, &lds)
+                                   : pdrnn_lstm_bidir_infer_plan((int)NL, (int)B, (int)T, &lds);
+    TORCH_CHECK(ns > 0, "bidirectional motion inference does not run NL=", NL, " B=", B, " T=", T,
+                " (one sequence's LDS exceeds 64 KiB)");
+    py::dict d;
+    d["ns"] = ns; d["lds"] = lds;
+    return d;
+  }, "sequences per workgroup and dynamic LDS bytes of lstm_bidir_head_infer for B sequences of T steps; raises "
+     "where T is too long for the LDS.  cus: for a device of that many compute units",
         py::arg("NL"), py::arg("B"), py::arg("T"), py::arg("cus") = py::none());
   m.def("lstm_small_supported", [](int64_t H, int64_t I, int64_t NL) {
     return pdrnn_lstm_small_supported((int)H, (int)I, (int)NL) != 0;

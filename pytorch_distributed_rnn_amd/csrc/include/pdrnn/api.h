@@ -216,6 +216,40 @@ int pdrnn_lstm_sw_infer_plan(int NL, int B, int T, int* map);
 int pdrnn_lstm_sw_infer_plan_cus(int NL, int B, int T, int cus, int* map);
 hipError_t pdrnn_lstm_sw_infer(const PdrnnLstmSmallFwdArgs* a, int mode, hipStream_t stream);
 
+// Bidirectional LSTM stack + head without gradients in one launch
+// (kernels/lstm_bidir_infer.hip): what pdrnn_lstm_sw_infer writes for the
+// unidirectional stack -- logits, pred, seq_stats -- from the head on
+// [h_fwd after T steps | h_bwd after its first step].  Parameters per
+// [layer][direction] (1 = nn.LSTM's *_reverse); biases are required; layer
+// 1's W_ih is [4H, 2H]; head_w is [C, 2H].
+typedef struct {
+  const float* x;            // fp32, element (b,t,i) at b*x_sb + t*x_st + i
+  const int64_t* idx;        // optional gather, as PdrnnLstmSmallFwdArgs
+  int64_t x_sb, x_st;
+  const float* w_ih[2][2];
+  const float* w_hh[2][2];
+  const float* b_ih[2][2];
+  const float* b_hh[2][2];
+  const float* head_w;       // [C, 2H]
+  const float* head_b;       // [C] or NULL
+  const int64_t* labels;     // [N] or NULL (indexed through idx when given)
+  float* logits;             // [B, C]
+  int64_t* pred;             // [B]
+  float* seq_stats;          // [B, 3] or NULL; requires labels
+  float inv_batch;
+  int C, B, T, I, NL;
+} PdrnnLstmBidirInferArgs;
+// 1 when the kernel serves the stack: H = 32, 1 <= I <= 12, 1 or 2 layers, LSTM (cell 0)
+int pdrnn_lstm_bidir_infer_ok(int H, int I, int NL, int cell);
+// Sequences per workgroup (grid = ceil(B / ns), 128 ns threads) and the
+// launch's dynamic LDS; 0 where one sequence's LDS exceeds 64 KiB (two
+// layers: T above 140, the layer-0 sequence buffers; one layer: T above 1348).
+int pdrnn_lstm_bidir_infer_plan(int NL, int B, int T, int* lds_bytes);
+int pdrnn_lstm_bidir_infer_plan_cus(int NL, int B, int T, int cus, int* lds_bytes);
+// hipErrorInvalidValue for a stack or head the kernel does not serve or a
+// missing pointer, hipErrorInvalidConfiguration when ns sequences exceed the LDS
+hipError_t pdrnn_lstm_bidir_infer(const PdrnnLstmBidirInferArgs* a, int ns, hipStream_t stream);
+
 // Column sums of a [rows, P] fp32 slab into out[P] (out = beta*out + sum).
 // Two deterministic passes through `work` ([split, P] floats, split <= 64)
 // (kernels/adam.hip, beside the fused step's one-pass pdrnn_slab_reduce_adam).

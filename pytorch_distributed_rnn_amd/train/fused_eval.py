@@ -15,6 +15,12 @@ model keeps ``model.forward``.  So does a batch whose sequences are too long
 for any wave map's LDS (``lstm_sw_infer_plan`` refuses it: T above ~1360):
 ``MotionEvalStep`` runs that batch through ``model.forward`` and adds its
 statistics into the same accumulator.
+
+A bidirectional fp32 LSTM stack of the same sizes (head ``Linear(2H, C)``) is
+one launch of ``lstm_bidir_head_infer`` (kernels/lstm_bidir_infer.hip), which
+writes the same three outputs; ``lstm_bidir_infer_plan`` refuses T above 140
+with two layers (1348 with one) and such a batch takes ``model.forward`` too.
+The bidirectional GRU and bf16 models keep ``model.forward``.
 """
 from __future__ import annotations
 
@@ -44,12 +50,14 @@ def supported(model: nn.Module, device: torch.device) -> bool:
         return False
     lstm = m.lstm
     # (lstm.dropout does not matter: evaluation applies none)
-    if lstm.bidirectional or getattr(lstm, "proj_size", 0) or not lstm.bias:
+    if getattr(lstm, "proj_size", 0) or not lstm.bias:
         return False
     cell = 1 if m.cell == "gru" else 0
-    if not mod.lstm_sw_ok(lstm.hidden_size, lstm.input_size, lstm.num_layers, cell):
+    ndir = 2 if lstm.bidirectional else 1
+    ok = mod.lstm_bidir_infer_ok if lstm.bidirectional else mod.lstm_sw_ok
+    if not ok(lstm.hidden_size, lstm.input_size, lstm.num_layers, cell):
         return False
-    if m.fc.out_features > 16 or m.fc.in_features != lstm.hidden_size:
+    if m.fc.out_features > 16 or m.fc.in_features != ndir * lstm.hidden_size:
         return False
     params = list(m.parameters())
     if any(p.dtype != torch.float32 for p in params):
@@ -57,8 +65,8 @@ def supported(model: nn.Module, device: torch.device) -> bool:
     if len({p.device for p in params}) != 1 or params[0].device.type != "cuda":
         return False  # (`device` may be a bare "cuda": the parameters say which GPU)
     cdt = getattr(m, "compute_dtype", torch.float32)
-    if m.cell == "gru":
-        return cdt == torch.float32  # the GRU runs the fp32 kernels only
+    if m.cell == "gru" or lstm.bidirectional:
+        return cdt == torch.float32  # the GRU and the bidirectional stack run the fp32 kernels only
     return cdt in (torch.float32, torch.bfloat16)
 
 
@@ -98,6 +106,7 @@ class MotionEvalStep:
         self.mod = _ext.native(dev)
         self.H, self.NL = m.lstm.hidden_size, m.lstm.num_layers
         self.gru = m.cell == "gru"
+        self.bidir = bool(m.lstm.bidirectional)
         self.bf16 = getattr(m, "compute_dtype", torch.float32) == torch.bfloat16
         self.acc = None  # [sum of batch mean losses, examples, correct], made by the first labelled batch
         self.batches = 0
@@ -115,7 +124,8 @@ class MotionEvalStep:
         """The stack's parameters as they are now (read per call: a module's
         parameters may be replaced)."""
         lstm = self.m.lstm
-        return [getattr(lstm, f"{k}_l{l}") for l in range(self.NL)
+        return [getattr(lstm, f"{k}_l{l}{sfx}") for l in range(self.NL)
+                for sfx in (("", "_reverse") if self.bidir else ("",))
                 for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
 
     def _operands(self, features: Tensor):
@@ -144,15 +154,21 @@ class MotionEvalStep:
             if labels.dtype != torch.int64 or not labels.is_contiguous():
                 labels = labels.long().contiguous()
         batch = idx.numel() if idx is not None else features.shape[0]
+        plan = self.mod.lstm_bidir_infer_plan if self.bidir else self.mod.lstm_sw_infer_plan
         try:
-            self.mod.lstm_sw_infer_plan(self.NL, batch, features.shape[1])
+            plan(self.NL, batch, features.shape[1])
         except RuntimeError:  # no wave map holds sequences this long in LDS
             return self._forward_batch(features, labels, idx)
         ws, features, cell = self._operands(features)
         if features.stride(2) != 1:
             features = features.contiguous()
-        logits, pred, seq_stats, _, _ = self.mod.lstm_head_infer(
-            features, idx, labels, ws, self.m.fc.weight, self.m.fc.bias, self.H, self.NL, cell, self.bf16, -1, False)
+        if self.bidir:
+            logits, pred, seq_stats = self.mod.lstm_bidir_head_infer(
+                features, idx, labels, ws, self.m.fc.weight, self.m.fc.bias, self.H, self.NL)
+        else:
+            logits, pred, seq_stats, _, _ = self.mod.lstm_head_infer(
+                features, idx, labels, ws, self.m.fc.weight, self.m.fc.bias, self.H, self.NL, cell, self.bf16, -1,
+                False)
         if seq_stats is not None:
             if self.acc is None:
                 self.acc = torch.zeros(3, dtype=torch.float32, device=seq_stats.device)
