@@ -3,7 +3,7 @@
 
 Times ``CharLM.generate`` at the char-LM configuration (2 x 1024 LSTM, embed
 256, vocabulary 256, bf16; 512 tokens after a one-token prompt) at B = 1, 4
-and 16 streams.  Both paths run in one process and alternate after a warm-up:
+and 16 streams (``--batches 32 48 64``: the wide-tile kernels).  Both paths run in one process and alternate after a warm-up:
 the fused path (kernels/lstm_decode.hip: layers + 1 launches per token, no
 host read) and the reference path (``PDRNN_KERNELS=torch`` is NOT what is
 meant: ``generate``'s token-by-token loop over ``forward`` on the training
@@ -136,7 +136,8 @@ def main(argv=None) -> int:
     torch.manual_seed(0)
     model = CharLM(args.vocab, args.embed, args.hidden, args.layers, compute_dtype=cdt, cell=args.cell).to(dev).eval()
     real_supported = dec.supported
-    covered = lambda B: real_supported(B, args.hidden, args.embed, args.vocab, args.layers, cdt, dev, args.cell)  # noqa: E731
+    # generate's own condition: batches past a call's streams run as groups (up to 64 streams on the wide-tile kernels)
+    covered = lambda B: real_supported(min(B, dec.MAX_STREAMS), args.hidden, args.embed, args.vocab, args.layers, cdt, dev, args.cell)  # noqa: E731
 
     def generate(prompt, fused: bool):
         # the reference path is generate's own: the shape reported as not covered

@@ -1909,10 +1909,11 @@ struct DecodeStack {
 // streams and N positions.
 // They run before the search's own G / W checks, so a search with too many
 // streams is refused here as "unsupported shape B=..." (B: its S = G W).
+// wide: the shape is held against the wide predicates (17 <= B <= 64) instead.
 DecodeStack check_decode_stack(const char* what, int cell, const Tensor& emb, const std::vector<Tensor>& w_ih,
                                const std::vector<Tensor>& w_hh, const std::vector<Tensor>& bias, const Tensor& w_fc,
                                const optional<Tensor>& b_fc, const Tensor& h, const Tensor& c, const Tensor& scratch,
-                               const Tensor& first, const optional<Tensor>& logits, int64_t N) {
+                               const Tensor& first, const optional<Tensor>& logits, int64_t N, bool wide = false) {
   const int dt = dtype_code(emb);
   const int64_t L = (int64_t)w_ih.size(), V = emb.size(0), E = emb.size(1);
   TORCH_CHECK(emb.dim() == 2 && emb.is_contiguous() && L >= 1 && (int64_t)w_hh.size() == L && (int64_t)bias.size() == L,
@@ -1920,8 +1921,9 @@ DecodeStack check_decode_stack(const char* what, int cell, const Tensor& emb, co
   TORCH_CHECK(h.dim() == 4 && h.size(0) == 2 && h.size(1) == L && h.is_contiguous() && h.is_cuda() && dtype_code(h) == dt,
               what, ": h [2, L, B, H] in the weights' dtype");
   const int64_t B = h.size(2), H = h.size(3);
-  const bool fits = cell == 0 ? pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt)
-                              : pdrnn_gru_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, dt);
+  const auto covers = wide ? (cell == 0 ? pdrnn_lstm_decode_wide_supported : pdrnn_gru_decode_wide_supported)
+                           : (cell == 0 ? pdrnn_lstm_decode_supported : pdrnn_gru_decode_supported);
+  const bool fits = covers((int)B, (int)H, (int)E, (int)V, (int)L, dt);
   TORCH_CHECK(fits && N >= 1,
               what, ": unsupported shape B=", B, " H=", H, " E=", E, " V=", V, " L=", L, " N=", N);
   DecodeStack d;
@@ -1965,21 +1967,24 @@ DecodeStack check_decode_stack(const char* what, int cell, const Tensor& emb, co
 // decode kernels, enqueued here in one go.  The buffers are the caller's (ops/decode.py).
 // CELL (PdrnnLstmDecodeStack's): _C.lstm_decode and _C.gru_decode (ops/gru_large.py's
 // zero-padded interleaved [4H, .] stacks; c: h's fp32 master).
+// WIDE: _C.lstm_decode_wide and _C.gru_decode_wide, the same arguments for 17 to 64 streams.
 constexpr const char* kDecodeName[] = {"lstm_decode", "gru_decode"};
+constexpr const char* kDecodeWideName[] = {"lstm_decode_wide", "gru_decode_wide"};
 constexpr const char* kDecodeBeamName[] = {"lstm_decode_beam", "gru_decode_beam"};
 
-template <int CELL>
+template <int CELL, bool WIDE = false>
 void decode_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
                  const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
                  const Tensor& c, const Tensor& scratch, const Tensor& first, const optional<Tensor>& forced,
                  const Tensor& tokens, const optional<Tensor>& logits, double temperature, int64_t seed,
                  int64_t stream0, int64_t pos0, int64_t top_k, double top_p, const optional<Tensor>& threshold,
                  const optional<Tensor>& logprobs) {
-  const char* what = kDecodeName[CELL];
+  const char* what = WIDE ? kDecodeWideName[CELL] : kDecodeName[CELL];
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
   const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
-  const DecodeStack d = check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+  const DecodeStack d =
+      check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N, WIDE);
   const int64_t B = d.stack.B;
   TORCH_CHECK(dev_i64(tokens) && tokens.size(0) == B, what, ": tokens [B, N] int64");
   if (present(forced)) TORCH_CHECK(dev_i64(*forced) && forced->dim() == 2 && forced->size(0) == B && forced->size(1) == N,
@@ -2002,7 +2007,11 @@ void decode_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
   a.top_p = (float)top_p;
   a.threshold = opt_mut(threshold);
   a.logprobs = opt_mut(logprobs);
-  HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
+  if constexpr (WIDE) {
+    HIP_LAUNCH_CHECK((CELL == 0 ? pdrnn_lstm_decode_wide : pdrnn_gru_decode_wide)(&a, (int)N, cur_stream()));
+  } else {
+    HIP_LAUNCH_CHECK(pdrnn_lstm_decode(&a, (int)N, cur_stream()));
+  }
 }
 
 // Beam search on the decode kernels: G groups of W beams; the buffers are the
@@ -2328,6 +2337,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");
   };
   def_supported("gru_decode_supported", &pdrnn_gru_decode_supported);
+  def_decode("lstm_decode_wide", &decode_cell<0, true>, "lstm_decode for 17 to 64 streams: the wide-tile kernels");
+  def_decode("gru_decode_wide", &decode_cell<1, true>, "gru_decode for 17 to 64 streams: the wide-tile kernels");
+  def_supported("lstm_decode_wide_supported", &pdrnn_lstm_decode_wide_supported);
+  def_supported("gru_decode_wide_supported", &pdrnn_gru_decode_wide_supported);
   m.def("lstm_decode_supported", [](int64_t B, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
     return pdrnn_lstm_decode_supported((int)B, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
   }, "the decode kernels cover the shape (dtype 0 bf16, 1 fp16, 2 fp32)");

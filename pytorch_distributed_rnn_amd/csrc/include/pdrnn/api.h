@@ -512,7 +512,7 @@ hipError_t pdrnn_slab_reduce_adam(const PdrnnAdamArgs* a, const float* A, int64_
 
 // ---- char-LM generation (kernels/lstm_decode.hip) --------------------------
 // One token of a unidirectional 16-bit LSTM stack with biases for B <= 16
-// streams is L launches of the decode layer kernel plus one of the vocabulary
+// streams (17 to 64: the _wide calls below) is L launches of the decode layer kernel plus one of the vocabulary
 // head.  The stack and its working buffers, common to sampling and beam search.
 // cell 1 is a GRU stack on the same launches: w_ih / w_hh are then the
 // zero-padded gate-interleaved stacks [r | z | n_x | 0] and [r | z | 0 | n_h]
@@ -562,6 +562,16 @@ hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStre
 // the limits of a GRU stack (cell 1) in pdrnn_lstm_decode / pdrnn_lstm_decode_beam: the LSTM's
 int pdrnn_gru_decode_supported(int B, int H, int E, int V, int L, int dtype);
 int pdrnn_gru_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype);
+// The wide tile: the same call for 17 <= B <= 64 streams on kernels that feed
+// ceil(B / 16) stream tiles of 16 from one weight load (the same launch count,
+// grids and buffers; a stream's results are bit for bit those of
+// pdrnn_lstm_decode on any 16 rows that hold it, stream0 moved along).  H, E,
+// V, L and dtype as in the 16-stream predicates.  pdrnn_lstm_decode_wide runs
+// the stack's cell; pdrnn_gru_decode_wide is the same call for cell 1 alone.
+int pdrnn_lstm_decode_wide_supported(int B, int H, int E, int V, int L, int dtype);
+int pdrnn_gru_decode_wide_supported(int B, int H, int E, int V, int L, int dtype);
+hipError_t pdrnn_lstm_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
+hipError_t pdrnn_gru_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
 
 // Beam search on the same kernels (pdrnn/decode_rng.h: the rule): G groups of W
 // beams, S = G W <= 16 streams, stream g W + j beam j of group g.  Selection q

@@ -47,6 +47,17 @@
 // (LayerArgs::c) and is updated in place like it; the 16-bit ping-pong h is
 // its rounding.
 //
+// The wide tile (lstm_decode_layer_wide, lstm_decode_head_wide; 17 to 64
+// streams): the weights are the A operand, so one weight load can feed several
+// stream tiles.  A wave loads its weight block once, the [x | h] block of NT =
+// 2, 3 or 4 tiles of 16 streams (a padding stream: a copy of the last stream's,
+// never stored), and issues NT MFMAs into NT accumulators, each
+// over the blocks kb = wave, wave + 8, ... in that order; wave j < NT then sums
+// tile j over the eight waves in wave order and runs its cell (the head: its
+// bias add and stores), the epilogues side by side.  A stream's accumulation
+// chain, reduction order and cell arithmetic are the 16-stream kernel's: its
+// h, c, logits and tokens do not depend on how the batch is tiled.
+//
 // Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) or
 // nn.GRU (r, z, n) + nn.Linear stepped one token at a time.
 #include <hip/hip_runtime.h>
@@ -669,6 +680,221 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_sample(const SampleArgs 
   record_sample<FILT>(s, s.N - 1, tok, thr, lp);
 }
 
+// ---- the wide tile: NT = 2, 3, 4 tiles of 16 streams per launch ----------------
+constexpr int kWideStreams = 4 * kStreams;
+// K blocks whose loads a wave issues before their MFMAs: 4 (1 + NT) uint4s, 12 to
+// 20, beside the 8 x 2 = 16 the 16-stream kernels' unroll asks for.
+constexpr int kWideUnroll = 4;
+
+// The wide kernels use plain fp32 operations only (no v_pk_*_f32; the same
+// target feature lstm_bidir_infer's build flag turns off for its whole file).
+// Helpers inlined into them are compiled the same way, and only an always_inline
+// function is inlined into one of other features: hence the lambda's attribute
+// and a barrier of their own, __syncthreads() word for word.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PDRNN_PLAIN_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define PDRNN_PLAIN_F32
+#endif
+
+__device__ __forceinline__ void workgroup_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <bool FILT>
+__device__ __forceinline__ void sample_position_wide(const SampleArgs& s, int p, int* tok, float* thr, float* lp) {
+  if constexpr (FILT)
+    with_slots(s.V, [&](auto ns) __attribute__((always_inline)) {
+      sample_tokens_filtered_n<decltype(ns)::value>(s, p, tok, thr, lp);
+    });
+  else sample_tokens(s, p, tok);
+}
+
+// Every wave's NT partial accumulators into LDS; on return (after the barrier)
+// wave j < NT holds tile j's sum over the waves in wave order 0..7, the order of
+// reduce_waves.  The waves past NT get tile 0's and have nothing to do with it.
+template <int NT>
+__device__ __forceinline__ f32x4 reduce_tiles(const f32x4 (&acc)[NT], f32x4 (*red)[NT][kWave]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) red[wave][j][lane] = acc[j];
+  workgroup_barrier();
+  const int j = wave < NT ? wave : 0;
+  f32x4 sum = red[0][j][lane];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) sum += red[w][j][lane];
+  return sum;
+}
+
+// A wave's K blocks kb = wave, wave + 8, ... < nkb in that order into each of the
+// NT accumulators: wload(kb) the weight operand, loaded once, vload(j, kb) tile
+// j's.  Four blocks at a time, every load issued before the first MFMA; the
+// blocks left over one by one.
+template <class DT, int NT, class WL, class VL>
+__device__ __forceinline__ void wide_k_loop(int nkb, f32x4 (&acc)[NT], WL wload, VL vload) {
+  constexpr int U = kWideUnroll;
+  int kb = threadIdx.x >> 6;
+  for (; kb + (U - 1) * kWaves < nkb; kb += U * kWaves) {
+    uint4 w[U], v[U][NT];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      w[u] = wload(kb + u * kWaves);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) v[u][j] = vload(j, kb + u * kWaves);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[j] = DT::mfma(w[u], v[u][j], acc[j]);
+    }
+  }
+  for (; kb < nkb; kb += kWaves) {
+    const uint4 w = wload(kb);
+    uint4 v[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) v[j] = vload(j, kb);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = DT::mfma(w, v[j], acc[j]);
+  }
+}
+
+// lstm_decode_layer for B in (16 (NT - 1), 16 NT] streams: stream 16 j + (lane &
+// 15) is column lane & 15 of tile j.  Sampling (Pick::sample, Pick::filtered) as
+// there, the LDS arrays 16 NT long; no beam search.
+template <class DT, bool FIRST, Pick PICK, Cell CELL, int NT>
+__global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_layer_wide(const LayerArgs a) {
+  static_assert(PICK != Pick::beam && (FIRST || PICK == Pick::sample), "sampling only; the filter is layer 0's");
+  static_assert(NT >= 2 && NT * kStreams <= kWideStreams, "2 to 4 tiles");
+  constexpr bool FILT = PICK == Pick::filtered;
+  constexpr int NS = NT * kStreams;
+  __shared__ f32x4 red[kWaves][NT][kWave];
+  __shared__ int tok[NS];
+  __shared__ float thr[FILT ? NS : 1], lp[FILT ? NS : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, kq = lane >> 4;
+  const int B = a.s.B, H = a.H, Kx = a.Kx;
+
+  if constexpr (FIRST) {
+    const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
+    if (sample) sample_position_wide<FILT>(a.s, a.p - 1, tok, thr, lp);
+    workgroup_barrier();
+    if (sample && blockIdx.x == 0) record_sample<FILT>(a.s, a.p - 1, tok, thr, lp);
+  }
+  // Tile j's operand rows of this lane.  A padding stream reads stream B - 1's
+  // rows: every load is then unconditional (a guarded uint4 load, also one whose
+  // value a select replaces by zero, compiles to four dword loads behind four
+  // branches here).  An MFMA column depends on its own B column alone and a
+  // padding column is never stored, so what it holds reaches nothing.
+  const uint16_t* xr[NT];
+  const uint16_t* hr[NT];
+  bool live[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    live[j] = j * kStreams + n < B;
+    const int s = live[j] ? j * kStreams + n : B - 1;
+    const uint16_t* xrow = a.x + (int64_t)s * Kx;
+    if constexpr (FIRST) {
+      int64_t t = 0;
+      if (live[j]) {
+        if (a.forced != nullptr) t = a.forced[(int64_t)s * a.s.N + a.p];
+        else if (a.p == 0) t = a.first[s];
+        else t = tok[s];
+        t = clamp_token(t, a.s.V);
+      }
+      xrow = a.x + t * Kx;
+    }
+    xr[j] = xrow + kq * 8;
+    hr[j] = a.hprev + (int64_t)s * H + kq * 8;
+  }
+
+  // the K blocks as in lstm_decode_layer: one weight load, NT operand loads, NT MFMAs
+  const int nkx = Kx / 32, nkb = nkx + H / 32;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int row = blockIdx.x * 16 + n;  // < 4H: the grid is H / 4
+  const uint16_t* wxr = a.wx + (int64_t)row * Kx + kq * 8;
+  const uint16_t* whr = a.wh + (int64_t)row * H + kq * 8;
+  wide_k_loop<DT, NT>(
+      nkb, acc,
+      [&](int kb) __attribute__((always_inline)) {
+        return *reinterpret_cast<const uint4*>(kb < nkx ? wxr + kb * 32 : whr + (kb - nkx) * 32);
+      },
+      [&](int j, int kb) __attribute__((always_inline)) {
+        return *reinterpret_cast<const uint4*>(kb < nkx ? xr[j] + kb * 32 : hr[j] + (kb - nkx) * 32);
+      });
+  const f32x4 z = reduce_tiles<NT>(acc, red);
+  const int s = wave * kStreams + n;  // wave j < NT: tile j's epilogue
+  if (wave >= NT || s >= B) return;
+
+  // lane: unit 4 blockIdx + (lane >> 4), stream s; the cell exactly as in lstm_decode_layer
+  const int u = blockIdx.x * 4 + kq;
+  const float* bs = a.bias + 4 * u;
+  const int64_t at = (int64_t)s * H + u;
+  if constexpr (CELL == Cell::lstm) {
+    const float gi = sigmoidf_fast(z[0] + bs[0]);
+    const float gf = sigmoidf_fast(z[1] + bs[1]);
+    const float gg = tanhf_fast(z[2] + bs[2]);
+    const float go = sigmoidf_fast(z[3] + bs[3]);
+    const float cn = fmaf(gf, a.c[at], gi * gg);
+    a.c[at] = cn;
+    a.hout[at] = DT::from_f(go * tanhf_fast(cn));
+  } else {
+    const float gr = sigmoidf_fast(z[0] + bs[0]);
+    const float gz = sigmoidf_fast(z[1] + bs[1]);
+    const float gn = tanhf_fast(fmaf(gr, z[3] + bs[3], z[2] + bs[2]));
+    float hn = fmaf(gz, a.c[at] - gn, gn);
+    asm volatile("" : "+v"(hn));  // (the 16-bit h is the rounding of the stored master, as there)
+    a.c[at] = hn;
+    a.hout[at] = DT::from_f(hn);
+  }
+}
+
+template <class DT, int NT>
+__global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_head_wide(const HeadArgs a) {
+  __shared__ f32x4 red[kWaves][NT][kWave];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, kq = lane >> 4;
+  const int H = a.H;
+  // vocabulary row of the A operand; the rows past V read row V - 1 and the padding streams stream B - 1
+  // (unconditional loads, as in the layer kernel: an output row or column that is never stored)
+  const int row = min(blockIdx.x * 16 + n, a.V - 1);
+  const uint16_t* wr = a.w + (int64_t)row * H + kq * 8;
+  const uint16_t* hr[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) hr[j] = a.h + (int64_t)min(j * kStreams + n, a.B - 1) * H + kq * 8;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  wide_k_loop<DT, NT>(
+      H / 32, acc,
+      [&](int kb) __attribute__((always_inline)) { return *reinterpret_cast<const uint4*>(wr + kb * 32); },
+      [&](int j, int kb) __attribute__((always_inline)) { return *reinterpret_cast<const uint4*>(hr[j] + kb * 32); });
+  const f32x4 z = reduce_tiles<NT>(acc, red);
+  const int s = wave * kStreams + n;
+  if (wave >= NT || s >= a.B) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int v = blockIdx.x * 16 + kq * 4 + i;
+    if (v >= a.V) break;
+    const float y = z[i] + (a.bias != nullptr ? a.bias[v] : 0.f);
+    a.scratch[(int64_t)s * a.V + v] = y;
+    if (a.logits != nullptr) a.logits[((int64_t)s * a.N + a.p) * a.V + v] = y;
+  }
+}
+
+// lstm_decode_sample for up to 64 streams
+template <bool FILT>
+__global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_sample_wide(const SampleArgs s) {
+  __shared__ int tok[kWideStreams];
+  __shared__ float thr[FILT ? kWideStreams : 1], lp[FILT ? kWideStreams : 1];
+  sample_position_wide<FILT>(s, s.N - 1, tok, thr, lp);
+  workgroup_barrier();
+  record_sample<FILT>(s, s.N - 1, tok, thr, lp);
+}
+
 // Selection q as a launch of its own (one workgroup): the one after the last
 // position.  hyp != null: the parents are then traced back, a thread per final
 // slot, into hyp [S, N] (and hyp_lp from lp), the last column from LDS.
@@ -690,8 +916,8 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs
 // The token loop of both modes: per position the layer-0 kernel of the mode,
 // the layers above and the head, L + 1 launches on the one stream.  k arrives
 // with the mode's part (s, b, forced) filled in; the caller enqueues the
-// mode's last launch.
-template <class DT, Pick PICK, Cell CELL>
+// mode's last launch.  NT > 1: the wide kernels of NT stream tiles, the same grids.
+template <class DT, Pick PICK, Cell CELL, int NT>
 hipError_t decode_positions_of(const PdrnnLstmDecodeStack& a, int n_tokens, LayerArgs k, hipStream_t stream) {
   constexpr Pick ABOVE = PICK == Pick::beam ? Pick::beam : Pick::sample;
   const int B = a.B, H = a.H, V = a.V, L = a.L;
@@ -712,23 +938,29 @@ hipError_t decode_positions_of(const PdrnnLstmDecodeStack& a, int n_tokens, Laye
       k.hout = hm + out + l * BH;
       k.c = a.c + l * BH;
       k.Kx = l == 0 ? a.E : H;
-      if (l == 0) lstm_decode_layer<DT, true, PICK, CELL><<<H / 4, kThreads, 0, stream>>>(k);
-      else lstm_decode_layer<DT, false, ABOVE, CELL><<<H / 4, kThreads, 0, stream>>>(k);
+      if constexpr (NT == 1) {
+        if (l == 0) lstm_decode_layer<DT, true, PICK, CELL><<<H / 4, kThreads, 0, stream>>>(k);
+        else lstm_decode_layer<DT, false, ABOVE, CELL><<<H / 4, kThreads, 0, stream>>>(k);
+      } else {
+        if (l == 0) lstm_decode_layer_wide<DT, true, PICK, CELL, NT><<<H / 4, kThreads, 0, stream>>>(k);
+        else lstm_decode_layer_wide<DT, false, ABOVE, CELL, NT><<<H / 4, kThreads, 0, stream>>>(k);
+      }
       PDRNN_HIP_CHECK(hipGetLastError());
     }
     const HeadArgs hd{static_cast<const uint16_t*>(a.w_fc), a.b_fc, h + out + (L - 1) * BH, a.scratch, a.logits,
                       B, H, V, n_tokens, p};
-    lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
+    if constexpr (NT == 1) lstm_decode_head<DT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
+    else lstm_decode_head_wide<DT, NT><<<(V + 15) / 16, kThreads, 0, stream>>>(hd);
     PDRNN_HIP_CHECK(hipGetLastError());
   }
   return hipSuccess;
 }
 
-template <class DT, Pick PICK>
+template <class DT, Pick PICK, int NT = 1>
 hipError_t decode_positions(const PdrnnLstmDecodeStack& a, int n_tokens, const LayerArgs& k, hipStream_t stream) {
   switch (a.cell) {
-    case 0: return decode_positions_of<DT, PICK, Cell::lstm>(a, n_tokens, k, stream);
-    case 1: return decode_positions_of<DT, PICK, Cell::gru>(a, n_tokens, k, stream);
+    case 0: return decode_positions_of<DT, PICK, Cell::lstm, NT>(a, n_tokens, k, stream);
+    case 1: return decode_positions_of<DT, PICK, Cell::gru, NT>(a, n_tokens, k, stream);
   }
   return hipErrorInvalidValue;
 }
@@ -752,7 +984,7 @@ hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream
   return hipGetLastError();
 }
 
-template <class DT>
+template <class DT, int NT = 1>
 hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
   const PdrnnLstmDecodeStack& st = a->stack;
   const bool top_k = a->top_k > 0 && a->top_k < st.V, top_p = a->top_p > 0.f && a->top_p < 1.f;
@@ -762,11 +994,27 @@ hipError_t decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream
   k.s = SampleArgs{st.scratch, a->tokens, st.B, st.V, n_tokens, a->temperature, a->seed, a->stream0, a->pos0,
                    top_k ? a->top_k : 0, top_p ? a->top_p : 0.f, a->threshold, a->logprobs};
   k.forced = a->forced;
-  PDRNN_HIP_CHECK(filt ? (decode_positions<DT, Pick::filtered>(st, n_tokens, k, stream))
-                       : (decode_positions<DT, Pick::sample>(st, n_tokens, k, stream)));
-  if (filt) lstm_decode_sample<true><<<1, kThreads, 0, stream>>>(k.s);
-  else lstm_decode_sample<false><<<1, kThreads, 0, stream>>>(k.s);
+  PDRNN_HIP_CHECK(filt ? (decode_positions<DT, Pick::filtered, NT>(st, n_tokens, k, stream))
+                       : (decode_positions<DT, Pick::sample, NT>(st, n_tokens, k, stream)));
+  if constexpr (NT == 1) {
+    if (filt) lstm_decode_sample<true><<<1, kThreads, 0, stream>>>(k.s);
+    else lstm_decode_sample<false><<<1, kThreads, 0, stream>>>(k.s);
+  } else {
+    if (filt) lstm_decode_sample_wide<true><<<1, kThreads, 0, stream>>>(k.s);
+    else lstm_decode_sample_wide<false><<<1, kThreads, 0, stream>>>(k.s);
+  }
   return hipGetLastError();
+}
+
+// the wide call by its tile count NT = ceil(B / 16)
+template <class DT>
+hipError_t decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
+  switch ((a->stack.B + kStreams - 1) / kStreams) {
+    case 2: return decode<DT, 2>(a, n_tokens, stream);
+    case 3: return decode<DT, 3>(a, n_tokens, stream);
+    case 4: return decode<DT, 4>(a, n_tokens, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -793,6 +1041,30 @@ hipError_t pdrnn_lstm_decode(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStre
   if (n_tokens < 1 || !pdrnn::stack_supported(st)) return hipErrorInvalidValue;
   if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
   return st.dtype == 0 ? pdrnn::decode<pdrnn::BF16>(a, n_tokens, stream) : pdrnn::decode<pdrnn::F16>(a, n_tokens, stream);
+}
+
+// 17 to 64 streams through the wide kernels; every other limit is the 16-stream predicate's
+int pdrnn_lstm_decode_wide_supported(int B, int H, int E, int V, int L, int dtype) {
+  return B > pdrnn::kStreams && B <= pdrnn::kWideStreams && pdrnn_lstm_decode_supported(pdrnn::kStreams, H, E, V, L, dtype);
+}
+
+int pdrnn_gru_decode_wide_supported(int B, int H, int E, int V, int L, int dtype) {
+  return B > pdrnn::kStreams && B <= pdrnn::kWideStreams && pdrnn_gru_decode_supported(pdrnn::kStreams, H, E, V, L, dtype);
+}
+
+hipError_t pdrnn_lstm_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
+  const PdrnnLstmDecodeStack& st = a->stack;
+  const bool fits = st.cell == 0   ? pdrnn_lstm_decode_wide_supported(st.B, st.H, st.E, st.V, st.L, st.dtype)
+                    : st.cell == 1 ? pdrnn_gru_decode_wide_supported(st.B, st.H, st.E, st.V, st.L, st.dtype)
+                                   : 0;
+  if (n_tokens < 1 || !fits) return hipErrorInvalidValue;
+  if (!(a->temperature >= 0.f) || a->top_k < 0 || !(a->top_p >= 0.f)) return hipErrorInvalidValue;
+  return st.dtype == 0 ? pdrnn::decode_wide<pdrnn::BF16>(a, n_tokens, stream)
+                       : pdrnn::decode_wide<pdrnn::F16>(a, n_tokens, stream);
+}
+
+hipError_t pdrnn_gru_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream) {
+  return a->stack.cell == 1 ? pdrnn_lstm_decode_wide(a, n_tokens, stream) : hipErrorInvalidValue;
 }
 
 int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, int dtype) {

@@ -165,8 +165,10 @@ class CharLM(nn.Module):
         read; the logits and the state are those of the full run.
 
         On the GPU, 16-bit models the decode kernels cover run on them
-        (kernels/lstm_decode.hip; more than 16 rows as independent groups of
-        16); everything else takes the reference path, ``forward`` one token at
+        (kernels/lstm_decode.hip; up to 64 rows in one call, on the wide-tile
+        kernels above 16; more as independent groups of 64, a remainder of 16
+        or fewer on the 16-stream kernels; a row's result does not depend on
+        the grouping); everything else takes the reference path, ``forward`` one token at
         a time -- an error under ``PDRNN_KERNELS=hip-strict``.  Dropout is off
         and the truncated-BPTT carry is left as it was."""
         from .. import _ext
@@ -188,8 +190,8 @@ class CharLM(nn.Module):
             filt = dict(top_k=top_k, top_p=top_p, return_logprobs=return_logprobs)
             if N > 0 and plain and dec.supported(min(B, dec.MAX_STREAMS), H, E, V, L, cdt, dev, self.cell):
                 outs = []
-                for b0 in range(0, B, dec.MAX_STREAMS):
-                    rows = slice(b0, min(b0 + dec.MAX_STREAMS, B))
+                for b0 in range(0, B, dec.MAX_WIDE_STREAMS):
+                    rows = slice(b0, min(b0 + dec.MAX_WIDE_STREAMS, B))
                     outs.append(dec.decode(
                         self.embedding.weight, self.rnn._weights(), self.fc.weight, self.fc.bias, cdt,
                         *self._entering(state, rows), first[rows], N, temperature=temperature, seed=seed, stream0=b0,

@@ -4,7 +4,10 @@ and the reference path.
 ``decode`` drives csrc/kernels/lstm_decode.hip: per generated token one launch
 per LSTM layer and one for the vocabulary head, all enqueued from C++ in one
 call, sampling inside the layer-0 launch of the next position; nothing is read
-back until the caller reads the tokens.  ``reference`` is the same generation
+back until the caller reads the tokens.  Up to 16 streams fill one MFMA tile;
+17 to 64 run on the wide-tile kernels (2 to 4 tiles fed from one weight load,
+the same launches), on which a stream's results are bit for bit what a call on
+any 16 of the rows gives it.  ``reference`` is the same generation
 as a host loop over a step function (``CharLM.forward`` one token at a time)
 and runs anywhere; both sample by the rule below.
 
@@ -81,10 +84,11 @@ from .lstm_large import _DTYPE_CODE, _bias_cat, shadow
 CELLS = ("lstm", "gru")
 
 __all__ = ["gumbel_noise", "keep_threshold", "token_logprobs", "check_filters", "sample", "supported", "alloc_buffers",
-           "decode", "reference", "MAX_STREAMS", "CELLS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
+           "decode", "reference", "MAX_STREAMS", "MAX_WIDE_STREAMS", "CELLS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
            "stop_lengths", "beam_finish", "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
 
-MAX_STREAMS = 16  # streams per launch: the 16-wide side of the MFMA tile
+MAX_STREAMS = 16  # streams of one MFMA tile (its 16-wide side): a beam search's limit
+MAX_WIDE_STREAMS = 64  # streams per launch of the wide-tile kernels: four tiles
 _M32 = 0xFFFFFFFF
 
 
@@ -218,8 +222,13 @@ def _covered(op: str, dtype: torch.dtype, device, *shape: int) -> bool:
 
 
 def supported(B: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device, cell: str = "lstm") -> bool:
-    """The fused decode kernels run this shape of a ``cell`` stack on ``device``."""
-    return _covered(_op(cell, "decode"), dtype, device, B, H, E, V, L)
+    """The fused decode kernels run this shape of a ``cell`` stack on ``device``: B <= 16 streams on the
+    16-stream kernels, 17 to 64 on the wide-tile ones."""
+    return _covered(_op(cell, _decode_op(B)), dtype, device, B, H, E, V, L)
+
+
+def _decode_op(B: int) -> str:
+    return "decode_wide" if B > MAX_STREAMS else "decode"
 
 
 def _op(cell: str, what: str) -> str:
@@ -300,7 +309,9 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
            seed: int = 0, stream0: int = 0, pos0: int = 0, forced: Optional[Tensor] = None,
            return_logits: bool = False, bufs: Optional[Dict[str, Optional[Tensor]]] = None, top_k: int = 0,
            top_p: float = 1.0, return_threshold: bool = False, return_logprobs: bool = False, cell: str = "lstm"):
-    """``num_tokens`` positions on the fused kernels for B <= 16 streams.
+    """``num_tokens`` positions on the fused kernels for B <= 64 streams: up to
+    16 on the 16-stream kernels, more on the wide-tile ones (the same buffers,
+    launches and, stream for stream, bits).
 
     emb_w [V, E], lstm_weights (w_ih, w_hh, b_ih, b_hh per layer), fc_w [V, H],
     fc_b: the fp32 masters; their 16-bit copies come from the shadow registry,
@@ -327,7 +338,7 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
             bufs = alloc_buffers(L, B, H, V, N, cdt, dev, return_logits, return_threshold, return_logprobs)
         h, c = bufs["h"], bufs["c"]
         _init_state(cell, h, c, h0, c0)
-        getattr(mod, _op(cell, "decode"))(
+        getattr(mod, _op(cell, _decode_op(B)))(
             *stack, h, c, bufs["scratch"], first.to(dev, torch.int64).contiguous(),
             forced.to(dev, torch.int64).contiguous() if forced is not None else None, bufs["tokens"],
             bufs["logits"] if return_logits else None, float(temperature), int(seed) & _M32,
