@@ -24,12 +24,16 @@ is the plain sampler the figures of profiles/r11 were taken with.
 ``--beam-width W ...``: beam search instead (``CharLM.beam_search``, one
 prompt): per width, the reference path, the fused path and plain fused
 sampling of W streams alternate in one process after the warm-up; one JSON
-line per width.
+line per width.  With ``--prompts G ...``: G prompts per call instead, the wide
+search (``beam_decode_wide``, up to 64 streams per launch) against the same
+prompts in chunks of ``16 // W`` (reached by making
+``ops.decode.beam_wide_supported`` answer no), alternated; one JSON line per
+(G, W) with 16 < G * W <= 64.
 
 ``--cell gru``: the same for a GRU model (``CharLM(cell="gru")``).
 
     python bench/decode_bench.py [--pairs 5] [--warmup 2] [--tokens 512] [--batches 1 4 16] [--out FILE]
-                                 [--top-k 40] [--top-p 0.9] [--logprobs] [--beam-width 1 4 16]
+                                 [--top-k 40] [--top-p 0.9] [--logprobs] [--beam-width 1 4 16 [--prompts 4 8]]
                                  [--cell gru]
 """
 from __future__ import annotations
@@ -105,6 +109,57 @@ def beam(args, model, dec, dev, cdt, generate) -> int:
     return 0
 
 
+def beam_wide(args, model, dec, dev, cdt) -> int:
+    """``--beam-width ... --prompts ...``: per (G, W) with 16 < G W <= 64 one JSON line.  After a warm-up two
+    ``CharLM.beam_search`` calls on G prompts alternate ``--pairs`` times: on the wide kernels (one launch
+    sequence) and in chunks of 16 // W prompts on the 16-stream kernels.  Microseconds per position of the call."""
+    real = dec.beam_wide_supported
+
+    def search(prompt, W, wide: bool):
+        dec.beam_wide_supported = real if wide else (lambda *a, **k: False)
+        try:
+            return model.beam_search(prompt, args.tokens, W)[0].cpu()
+        finally:
+            dec.beam_wide_supported = real
+
+    def timed(fn) -> float:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / args.tokens
+
+    def summary(xs):
+        return {"median": round(statistics.median(xs), 2), "min": round(min(xs), 2), "max": round(max(xs), 2)}
+
+    lines = []
+    for W in args.beam_width:
+        for G in args.prompts:
+            if not dec.MAX_STREAMS < G * W <= dec.MAX_WIDE_STREAMS:
+                continue
+            assert real(G, W, args.hidden, args.embed, args.vocab, args.layers, cdt, dev, args.cell), \
+                f"the wide decode kernels do not cover G = {G}, W = {W}"
+            prompt = (torch.arange(G, device=dev)[:, None] * 7 + 1) % args.vocab
+            for _ in range(args.warmup):
+                chunked, wide = search(prompt, W, False), search(prompt, W, True)
+            pairs = [(timed(lambda: search(prompt, W, False)), timed(lambda: search(prompt, W, True)))
+                     for _ in range(args.pairs)]
+            rec = {"prompts": G, "beam_width": W, "tokens": args.tokens,
+                   "model": f"{args.cell} {args.layers}x{args.hidden} E{args.embed} V{args.vocab} {args.dtype}",
+                   "pairs_us_per_token": [[round(a, 2), round(b, 2)] for a, b in pairs],
+                   "chunked_us_per_token": summary([a for a, _ in pairs]),
+                   "wide_us_per_token": summary([b for _, b in pairs]),
+                   "wide_wins_every_pair": all(b < a for a, b in pairs),
+                   "hypotheses_equal": bool(torch.equal(chunked, wide))}
+            rec["speedup_of_medians"] = round(rec["chunked_us_per_token"]["median"] / rec["wide_us_per_token"]["median"], 2)
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--pairs", type=int, default=5)
@@ -122,6 +177,8 @@ def main(argv=None) -> int:
     ap.add_argument("--logprobs", action="store_true", help="also return the tokens' log-probabilities")
     ap.add_argument("--beam-width", type=int, nargs="+", default=None, metavar="W",
                     help="time beam search at these widths instead (one prompt per call)")
+    ap.add_argument("--prompts", type=int, nargs="+", default=None, metavar="G",
+                    help="with --beam-width: G prompts per call, the wide search against chunks of 16 streams")
     ap.add_argument("--cell", choices=("lstm", "gru"), default="lstm")
     ap.add_argument("--profile-one", type=int, default=None, metavar="B")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
@@ -160,6 +217,8 @@ def main(argv=None) -> int:
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e6 / args.tokens
 
+    if args.beam_width and args.prompts:
+        return beam_wide(args, model, dec, dev, cdt)
     if args.beam_width:
         return beam(args, model, dec, dev, cdt, generate)
 

@@ -1971,6 +1971,7 @@ DecodeStack check_decode_stack(const char* what, int cell, const Tensor& emb, co
 constexpr const char* kDecodeName[] = {"lstm_decode", "gru_decode"};
 constexpr const char* kDecodeWideName[] = {"lstm_decode_wide", "gru_decode_wide"};
 constexpr const char* kDecodeBeamName[] = {"lstm_decode_beam", "gru_decode_beam"};
+constexpr const char* kDecodeBeamWideName[] = {"lstm_decode_beam_wide", "gru_decode_beam_wide"};
 
 template <int CELL, bool WIDE = false>
 void decode_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
@@ -2016,24 +2017,26 @@ void decode_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::
 
 // Beam search on the decode kernels: G groups of W beams; the buffers are the
 // caller's (ops/decode.py:alloc_beam_buffers), cum / done row 0 filled.
-template <int CELL>
+// WIDE: _C.lstm_decode_beam_wide and _C.gru_decode_beam_wide, the same arguments for 17 to 64 streams.
+template <int CELL, bool WIDE = false>
 void decode_beam_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const std::vector<Tensor>& w_hh,
                       const std::vector<Tensor>& bias, const Tensor& w_fc, const optional<Tensor>& b_fc, const Tensor& h,
                       const Tensor& c, const Tensor& scratch, const Tensor& first, const Tensor& cum, const Tensor& done,
                       const Tensor& tokens, const Tensor& parents, const optional<Tensor>& lp,
                       const optional<Tensor>& logits, const Tensor& hyp, const optional<Tensor>& hyp_lp, int64_t G,
                       int64_t W, int64_t stop) {
-  const char* what = kDecodeBeamName[CELL];
+  const char* what = WIDE ? kDecodeBeamWideName[CELL] : kDecodeBeamName[CELL];
   CHECK_HIP_TENSOR(emb);
   const c10::DeviceGuard guard(emb.device());
   const int64_t N = tokens.dim() == 2 ? tokens.size(1) : 0;
   const DecodeStack d =
-      check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N);
+      check_decode_stack(what, CELL, emb, w_ih, w_hh, bias, w_fc, b_fc, h, c, scratch, first, logits, N, WIDE);
   const PdrnnLstmDecodeStack& s = d.stack;
   const int64_t S = s.B;
-  TORCH_CHECK(G >= 1 && W >= 1 && G <= 16 && W <= 16 && G * W == S &&
-              (CELL == 0 ? pdrnn_lstm_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype)
-                         : pdrnn_gru_decode_beam_supported((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype)),
+  const auto covers = WIDE ? (CELL == 0 ? pdrnn_lstm_decode_beam_wide_supported : pdrnn_gru_decode_beam_wide_supported)
+                           : (CELL == 0 ? pdrnn_lstm_decode_beam_supported : pdrnn_gru_decode_beam_supported);
+  TORCH_CHECK(G >= 1 && W >= 1 && G <= (WIDE ? 64 : 16) && W <= 16 && G * W == S &&
+              covers((int)G, (int)W, s.H, s.E, s.V, s.L, s.dtype),
               what, ": unsupported shape G=", G, " W=", W, " S=", S, " H=", s.H, " E=", s.E, " V=", s.V,
               " L=", s.L, " N=", N);
   TORCH_CHECK(stop >= -1 && stop < s.V, what, ": stop in [0, V), or -1 for none");
@@ -2058,7 +2061,7 @@ void decode_beam_cell(const Tensor& emb, const std::vector<Tensor>& w_ih, const 
   a.hyp_lp = opt_mut(hyp_lp);
   a.G = (int)G; a.W = (int)W;
   a.stop = (int)stop;
-  HIP_LAUNCH_CHECK(pdrnn_lstm_decode_beam(&a, (int)N, cur_stream()));
+  HIP_LAUNCH_CHECK((WIDE ? pdrnn_lstm_decode_beam_wide : pdrnn_lstm_decode_beam)(&a, (int)N, cur_stream()));
 }
 
 // ONE beam selection on the caller's logits [S, V], cum [S], done [S] (bool)
@@ -2352,6 +2355,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   };
   def_beam("lstm_decode_beam", &decode_beam_cell<0>, "char-LM beam search: n_tokens positions of the fused decode kernels");
   def_beam("gru_decode_beam", &decode_beam_cell<1>, "lstm_decode_beam for a GRU stack (gru_decode's operands)");
+  def_beam("lstm_decode_beam_wide", &decode_beam_cell<0, true>, "lstm_decode_beam for 17 to 64 streams: the wide-tile kernels");
+  def_beam("gru_decode_beam_wide", &decode_beam_cell<1, true>, "gru_decode_beam for 17 to 64 streams: the wide-tile kernels");
+  auto def_beam_supported = [&m](const char* name, int (*fn)(int, int, int, int, int, int, int)) {
+    m.def(name, [fn](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
+      auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
+      return fits(G) && fits(W) && fits(H) && fits(E) && fits(V) && fits(L) &&
+             fn((int)G, (int)W, (int)H, (int)E, (int)V, (int)L, (int)dtype) != 0;
+    }, "the wide-tile decode kernels cover a beam search of G groups of W beams, 17 <= G W <= 64 (dtype 0 bf16, 1 fp16, 2 fp32)");
+  };
+  def_beam_supported("lstm_decode_beam_wide_supported", &pdrnn_lstm_decode_beam_wide_supported);
+  def_beam_supported("gru_decode_beam_wide_supported", &pdrnn_gru_decode_beam_wide_supported);
   m.def("gru_decode_beam_supported",
         [](int64_t G, int64_t W, int64_t H, int64_t E, int64_t V, int64_t L, int64_t dtype) {
           auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };

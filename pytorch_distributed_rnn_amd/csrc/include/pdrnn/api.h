@@ -574,7 +574,8 @@ hipError_t pdrnn_lstm_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hi
 hipError_t pdrnn_gru_decode_wide(const PdrnnLstmDecodeArgs* a, int n_tokens, hipStream_t stream);
 
 // Beam search on the same kernels (pdrnn/decode_rng.h: the rule): G groups of W
-// beams, S = G W <= 16 streams, stream g W + j beam j of group g.  Selection q
+// beams, S = G W <= 16 streams (17 to 64: the _beam_wide call below), stream
+// g W + j beam j of group g.  Selection q
 // (on position q's logits) runs inside the layer-0 launch of position q + 1,
 // the last one in a launch of its own that also traces the parents back.
 typedef struct {
@@ -595,6 +596,16 @@ int pdrnn_lstm_decode_beam_supported(int G, int W, int H, int E, int V, int L, i
 // Enqueues (L + 1) * n_tokens launches and the last selection; no host read.
 // Bad arguments (a shape not supported, stack.B != G W, n_tokens < 1, stop outside [-1, V)) are hipErrorInvalidValue.
 hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream);
+// The wide search: the same call for 17 <= G W <= 64 streams, 1 <= W <= 16, on
+// the wide-tile kernels (the same launch count and buffers; a group may lie
+// across a tile of 16).  A group's hypotheses, scores, log-probs, state and
+// per-position record are bit for bit those of pdrnn_lstm_decode_beam on any
+// call that holds the group (parents relative to the group's first stream).
+// H, E, V, L and dtype as in the 16-stream predicates; the call runs the
+// stack's cell.  Bad arguments are hipErrorInvalidValue, as there.
+int pdrnn_lstm_decode_beam_wide_supported(int G, int W, int H, int E, int V, int L, int dtype);
+int pdrnn_gru_decode_beam_wide_supported(int G, int W, int H, int E, int V, int L, int dtype);
+hipError_t pdrnn_lstm_decode_beam_wide(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream);
 // ONE selection through the last position's kernel: logits [S, V], cum / done
 // [2, S] (row 0 read, row 1 written), tokens / parents / lp [S].
 hipError_t pdrnn_lstm_decode_beam_select(const float* logits, float* cum, int32_t* done, int64_t* tokens,

@@ -56,7 +56,10 @@
 // tile j over the eight waves in wave order and runs its cell (the head: its
 // bias add and stores), the epilogues side by side.  A stream's accumulation
 // chain, reduction order and cell arithmetic are the 16-stream kernel's: its
-// h, c, logits and tokens do not depend on how the batch is tiled.
+// h, c, logits and tokens do not depend on how the batch is tiled.  The wide
+// beam search (the Pick::beam instantiations of lstm_decode_layer_wide,
+// lstm_decode_beam_pick_wide): G W in (16, 64] streams, groups free to lie
+// across tile boundaries; a group's search is bit for bit the 16-stream one.
 //
 // Reference semantics: torch.nn.Embedding + nn.LSTM (gate order i, f, g, o) or
 // nn.GRU (r, z, n) + nn.Linear stepped one token at a time.
@@ -359,25 +362,46 @@ struct BeamArgs {
   int stop;              // -1: none
 };
 
-struct BeamLds {
-  uint32_t ck[kStreams][kStreams];  // a stream's W best candidates in rank order: score keys (0: none),
-  int cv[kStreams][kStreams];       // tokens
-  float cl[kStreams][kStreams];     // and log-probs
-  int parent[kStreams], tok[kStreams], done[kStreams];  // the new slots
-  float cum[kStreams], lp[kStreams];
+// A stream's W best candidates in rank order, for up to MAXS streams.
+template <int MAXS>
+struct BeamCands {
+  uint32_t ck[MAXS][kStreams];  // score keys (0: none),
+  int cv[MAXS][kStreams];       // tokens
+  float cl[MAXS][kStreams];     // and log-probs
+};
+// the new slots
+template <int MAXS>
+struct BeamSlots {
+  int parent[MAXS], tok[MAXS], done[MAXS];
+  float cum[MAXS], lp[MAXS];
+};
+template <int MAXS>
+struct BeamLdsOf {
+  BeamCands<MAXS> c;
+  BeamSlots<MAXS> s;
+};
+typedef BeamLdsOf<kStreams> BeamLds;
+
+// The workgroup barrier of a selection: the wide kernels have their own (below).
+struct BlockSync {
+  static __device__ __forceinline__ void sync() { __syncthreads(); }
 };
 
-// One selection, by every lane of the workgroup; the new slots end in L.
-//   1. A wave per stream, the row in registers as in sample_tokens_filtered_n:
-//      log-softmax, score keys, then the row's W best in rank order by W rounds
-//      of (wave max of the keys, first holder by ballots: the lowest slot, then
-//      the lowest lane, is the lowest v), into LDS.  A stream contributes at
-//      most W winners, and they are among these.
-//   2. A wave per group: lane j < W holds the head of stream j's list; W rounds
-//      of (wave max of the heads, the lowest lane holding it) merge them.
-// Integer keys, ballots and fixed-order sums: the same bits in every workgroup.
-template <int NS>
-__device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds& L) {
+// One selection, by every lane of the workgroup; the candidate lists in C, the
+// new slots end in L (MAXS streams at the most; SYNC: the workgroup's barrier).
+//   1. A wave per stream (waves take streams wave, wave + 8, ...), the row in
+//      registers as in sample_tokens_filtered_n: log-softmax, score keys, then
+//      the row's W best in rank order by W rounds of (wave max of the keys,
+//      first holder by ballots: the lowest slot, then the lowest lane, is the
+//      lowest v), into LDS.  A stream contributes at most W winners, and they
+//      are among these.
+//   2. A wave per group (groups wave, wave + 8, ...): lane j < W holds the head
+//      of stream j's list; W rounds of (wave max of the heads, the lowest lane
+//      holding it) merge them.
+// Integer keys, ballots and fixed-order sums: the same bits in every workgroup,
+// and for a group the same bits whichever launch holds it, and wherever in it.
+template <int NS, class SYNC, int MAXS>
+__device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamCands<MAXS>& C, BeamSlots<MAXS>& L) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int V = b.V, W = b.W, S = b.G * b.W;
   const float* cum = b.cum + (int64_t)q * S;
@@ -433,43 +457,44 @@ __device__ __forceinline__ void beam_select_n(const BeamArgs& b, int q, BeamLds&
         }
       }
       if (lane == 0) {
-        L.ck[s][r] = mx;
-        L.cv[s][r] = wv;
-        L.cl[s][r] = wl;
+        C.ck[s][r] = mx;
+        C.cv[s][r] = wv;
+        C.cl[s][r] = wl;
       }
     }
   }
-  __syncthreads();
+  SYNC::sync();
   for (int g = wave; g < b.G; g += kWaves) {
     const int s = g * W + (lane < W ? lane : 0);
     int head = 0;
 #pragma unroll 1
     for (int i = 0; i < W; ++i) {
-      const uint32_t k = lane < W && head < W ? L.ck[s][head] : 0;
+      const uint32_t k = lane < W && head < W ? C.ck[s][head] : 0;
       const uint32_t mx = wave_reduce<Max>(k);
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(lane < W && k == mx);
       const int j = __builtin_ctzll(bal);  // (a group always has W candidates: lane 0 at the worst)
       PDRNN_DEVICE_ASSERT(mx != 0);
       if (lane == j) {
-        const int slot = g * W + i, v = head < W ? L.cv[s][head] : 0;
+        const int slot = g * W + i, v = head < W ? C.cv[s][head] : 0;
         L.parent[slot] = s;
         L.tok[slot] = v;
         L.cum[slot] = mx != 0 ? decode_key_value(mx) : -INFINITY;
-        L.lp[slot] = head < W ? L.cl[s][head] : 0.f;
+        L.lp[slot] = head < W ? C.cl[s][head] : 0.f;
         L.done[slot] = done[s] != 0 || v == b.stop;
         ++head;
       }
     }
   }
-  __syncthreads();
+  SYNC::sync();
 }
 
 __device__ __forceinline__ void beam_select(const BeamArgs& b, int q, BeamLds& L) {
-  with_slots(b.V, [&](auto ns) { beam_select_n<decltype(ns)::value>(b, q, L); });
+  with_slots(b.V, [&](auto ns) { beam_select_n<decltype(ns)::value, BlockSync>(b, q, L.c, L.s); });
 }
 
 // selection q's record (one workgroup's job)
-__device__ __forceinline__ void beam_record(const BeamArgs& b, int q, const BeamLds& L) {
+template <int MAXS>
+__device__ __forceinline__ void beam_record(const BeamArgs& b, int q, const BeamSlots<MAXS>& L) {
   const int S = b.G * b.W, s = threadIdx.x;
   if (s >= S) return;
   const int64_t at = (int64_t)s * b.N + q;
@@ -554,12 +579,12 @@ __global__ __launch_bounds__(kThreads) void lstm_decode_layer(const LayerArgs a)
     __shared__ BeamLds L;
     if (a.p > 0) {
       beam_select(a.b, a.p - 1, L);
-      if (blockIdx.x == 0) beam_record(a.b, a.p - 1, L);
+      if (blockIdx.x == 0) beam_record(a.b, a.p - 1, L.s);
     }
     int64_t t = 0;
     if (live) {
       if (a.p == 0) t = a.first[n];
-      else t = L.tok[n], par = L.parent[n];
+      else t = L.s.tok[n], par = L.s.parent[n];
       t = clamp_token(t, a.s.V);
       par = beam_parent(par, n, a.b.W);
     }
@@ -712,6 +737,35 @@ __device__ __forceinline__ void sample_position_wide(const SampleArgs& s, int p,
   else sample_tokens(s, p, tok);
 }
 
+struct WideSync {
+  static __device__ __forceinline__ void sync() { workgroup_barrier(); }
+};
+
+// beam_select for G W in (16, 64] streams: the same two steps, the same
+// arithmetic of a row and the same integer keys, over more rows and more groups
+// -- step 1 is up to eight rows per wave (W rounds each), step 2 up to eight
+// groups per wave (W = 1: 64 groups) -- with the wide kernels' own barrier.
+__device__ __forceinline__ void beam_select_wide(const BeamArgs& b, int q, BeamCands<kWideStreams>& C,
+                                                 BeamSlots<kWideStreams>& L) {
+  with_slots(b.V, [&](auto ns) __attribute__((always_inline)) {
+    beam_select_n<decltype(ns)::value, WideSync>(b, q, C, L);
+  });
+}
+
+// The wide layer kernel's LDS.  The K loop's reduction buffer is the large
+// part (8 KB a tile); a search's candidate lists (12 KB) lie in the same
+// storage: the selection's last barrier comes after the last read of a list,
+// and the first write of a partial sum after that barrier.
+template <int NT, bool BEAM>
+union WideLds {
+  f32x4 red[kWaves][NT][kWave];
+};
+template <int NT>
+union WideLds<NT, true> {
+  f32x4 red[kWaves][NT][kWave];
+  BeamCands<kWideStreams> cand;
+};
+
 // Every wave's NT partial accumulators into LDS; on return (after the barrier)
 // wave j < NT holds tile j's sum over the waves in wave order 0..7, the order of
 // reduce_waves.  The waves past NT get tile 0's and have nothing to do with it.
@@ -762,21 +816,40 @@ __device__ __forceinline__ void wide_k_loop(int nkb, f32x4 (&acc)[NT], WL wload,
 
 // lstm_decode_layer for B in (16 (NT - 1), 16 NT] streams: stream 16 j + (lane &
 // 15) is column lane & 15 of tile j.  Sampling (Pick::sample, Pick::filtered) as
-// there, the LDS arrays 16 NT long; no beam search.
+// there, the LDS arrays 16 NT long.
+//
+// Pick::beam: G groups of W beams are the B = G W streams, as in
+// lstm_decode_layer, and a group may lie across a tile boundary (W = 3: group 5
+// is streams 15, 16, 17).  Tile j's operand rows of h_{t-1} are then rows of
+// parents that may belong to tile j - 1 or j + 1: plain row reads.  The in-place
+// c (the GRU: fp32 h) is the one hazard: wave j runs tile j's epilogue, and wave
+// 0 would store c[15] while wave 1 still has to load it as the parent of stream
+// 16.  So every epilogue wave loads c[par] and has the value in a register (the
+// empty asm that uses it makes the compiler wait for the load) BEFORE a
+// workgroup barrier that all eight waves reach, and stores c[s] AFTER it: every
+// load of the unit's c has completed before any store to it.  No other
+// workgroup touches the unit.
 template <class DT, bool FIRST, Pick PICK, Cell CELL, int NT>
 __global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_layer_wide(const LayerArgs a) {
-  static_assert(PICK != Pick::beam && (FIRST || PICK == Pick::sample), "sampling only; the filter is layer 0's");
+  static_assert(FIRST || PICK != Pick::filtered, "the filter is layer 0's");
   static_assert(NT >= 2 && NT * kStreams <= kWideStreams, "2 to 4 tiles");
-  constexpr bool FILT = PICK == Pick::filtered;
+  constexpr bool FILT = PICK == Pick::filtered, BEAM = PICK == Pick::beam;
   constexpr int NS = NT * kStreams;
-  __shared__ f32x4 red[kWaves][NT][kWave];
-  __shared__ int tok[NS];
+  __shared__ WideLds<NT, BEAM> lds;
+  auto& red = lds.red;
+  __shared__ int tok[BEAM ? 1 : NS];
   __shared__ float thr[FILT ? NS : 1], lp[FILT ? NS : 1];
+  __shared__ BeamSlots<BEAM && FIRST ? kWideStreams : 1> slots;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 15, kq = lane >> 4;
   const int B = a.s.B, H = a.H, Kx = a.Kx;
 
-  if constexpr (FIRST) {
+  if constexpr (BEAM && FIRST) {
+    if (a.p > 0) {
+      beam_select_wide(a.b, a.p - 1, lds.cand, slots);
+      if (blockIdx.x == 0) beam_record(a.b, a.p - 1, slots);
+    }
+  } else if constexpr (FIRST) {
     const bool sample = a.p > 0 && (a.forced == nullptr || blockIdx.x == 0);
     if (sample) sample_position_wide<FILT>(a.s, a.p - 1, tok, thr, lp);
     workgroup_barrier();
@@ -790,12 +863,20 @@ __global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_layer_wi
   const uint16_t* xr[NT];
   const uint16_t* hr[NT];
   bool live[NT];
+  int pe = 0;  // Pick::beam: the parent of this lane's epilogue stream 16 wave + n
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     live[j] = j * kStreams + n < B;
     const int s = live[j] ? j * kStreams + n : B - 1;
+    int par = s;  // the stream whose state stream s continues (a padding stream: stream B - 1's)
     const uint16_t* xrow = a.x + (int64_t)s * Kx;
-    if constexpr (FIRST) {
+    if constexpr (BEAM && FIRST) {
+      int64_t t = a.first[s];
+      if (a.p > 0) t = slots.tok[s], par = slots.parent[s];
+      xrow = a.x + clamp_token(t, a.s.V) * Kx;
+    } else if constexpr (BEAM) {
+      if (a.p > 0) par = a.b.parents[(int64_t)s * a.b.N + a.p - 1];
+    } else if constexpr (FIRST) {
       int64_t t = 0;
       if (live[j]) {
         if (a.forced != nullptr) t = a.forced[(int64_t)s * a.s.N + a.p];
@@ -805,8 +886,12 @@ __global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_layer_wi
       }
       xrow = a.x + t * Kx;
     }
+    if constexpr (BEAM) {
+      par = beam_parent(par, s, a.b.W);
+      if (wave == j) pe = par;
+    }
     xr[j] = xrow + kq * 8;
-    hr[j] = a.hprev + (int64_t)s * H + kq * 8;
+    hr[j] = a.hprev + (int64_t)par * H + kq * 8;
   }
 
   // the K blocks as in lstm_decode_layer: one weight load, NT operand loads, NT MFMAs
@@ -827,25 +912,35 @@ __global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_layer_wi
       });
   const f32x4 z = reduce_tiles<NT>(acc, red);
   const int s = wave * kStreams + n;  // wave j < NT: tile j's epilogue
-  if (wave >= NT || s >= B) return;
+  const bool mine = wave < NT && s < B;
+  float cpar = 0.f;  // Pick::beam: the parent's c (the GRU: fp32 h)
+  if constexpr (BEAM) {
+    // which another wave's tile may hold: loaded, and arrived, before the barrier that every
+    // wave reaches; the stores below come after it (see above the kernel)
+    if (mine) cpar = a.c[(int64_t)pe * H + blockIdx.x * 4 + kq];
+    asm volatile("" : "+v"(cpar));
+    workgroup_barrier();
+  }
+  if (!mine) return;
 
   // lane: unit 4 blockIdx + (lane >> 4), stream s; the cell exactly as in lstm_decode_layer
   const int u = blockIdx.x * 4 + kq;
   const float* bs = a.bias + 4 * u;
   const int64_t at = (int64_t)s * H + u;
+  const float cp = BEAM ? cpar : a.c[at];  // c (the GRU: fp32 h) entering the position
   if constexpr (CELL == Cell::lstm) {
     const float gi = sigmoidf_fast(z[0] + bs[0]);
     const float gf = sigmoidf_fast(z[1] + bs[1]);
     const float gg = tanhf_fast(z[2] + bs[2]);
     const float go = sigmoidf_fast(z[3] + bs[3]);
-    const float cn = fmaf(gf, a.c[at], gi * gg);
+    const float cn = fmaf(gf, cp, gi * gg);
     a.c[at] = cn;
     a.hout[at] = DT::from_f(go * tanhf_fast(cn));
   } else {
     const float gr = sigmoidf_fast(z[0] + bs[0]);
     const float gz = sigmoidf_fast(z[1] + bs[1]);
     const float gn = tanhf_fast(fmaf(gr, z[3] + bs[3], z[2] + bs[2]));
-    float hn = fmaf(gz, a.c[at] - gn, gn);
+    float hn = fmaf(gz, cp - gn, gn);
     asm volatile("" : "+v"(hn));  // (the 16-bit h is the rounding of the stored master, as there)
     a.c[at] = hn;
     a.hout[at] = DT::from_f(hn);
@@ -901,15 +996,33 @@ __global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_sample_w
 __global__ __launch_bounds__(kThreads) void lstm_decode_beam_pick(const BeamArgs b, int q, int64_t* hyp, float* hyp_lp) {
   __shared__ BeamLds L;
   beam_select(b, q, L);
-  beam_record(b, q, L);
+  beam_record(b, q, L.s);
   const int S = b.G * b.W, i = threadIdx.x;
   if (hyp == nullptr || i >= S) return;
   int at = i;
   for (int k = q; k >= 0; --k) {
     const int64_t src = (int64_t)at * b.N + k, dst = (int64_t)i * b.N + k;
-    hyp[dst] = k == q ? L.tok[at] : b.tokens[src];
-    if (hyp_lp != nullptr) hyp_lp[dst] = k == q ? L.lp[at] : b.lp[src];
-    at = beam_parent(k == q ? L.parent[at] : b.parents[src], at, b.W);
+    hyp[dst] = k == q ? L.s.tok[at] : b.tokens[src];
+    if (hyp_lp != nullptr) hyp_lp[dst] = k == q ? L.s.lp[at] : b.lp[src];
+    at = beam_parent(k == q ? L.s.parent[at] : b.parents[src], at, b.W);
+  }
+}
+
+// lstm_decode_beam_pick for up to 64 final slots (the same lines: written once as a shared
+// helper they changed the 16-stream kernel's code)
+__global__ __launch_bounds__(kThreads) PDRNN_PLAIN_F32 void lstm_decode_beam_pick_wide(const BeamArgs b, int q, int64_t* hyp,
+                                                                                        float* hyp_lp) {
+  __shared__ BeamLdsOf<kWideStreams> L;
+  beam_select_wide(b, q, L.c, L.s);
+  beam_record(b, q, L.s);
+  const int S = b.G * b.W, i = threadIdx.x;
+  if (hyp == nullptr || i >= S) return;
+  int at = i;
+  for (int k = q; k >= 0; --k) {
+    const int64_t src = (int64_t)at * b.N + k, dst = (int64_t)i * b.N + k;
+    hyp[dst] = k == q ? L.s.tok[at] : b.tokens[src];
+    if (hyp_lp != nullptr) hyp_lp[dst] = k == q ? L.s.lp[at] : b.lp[src];
+    at = beam_parent(k == q ? L.s.parent[at] : b.parents[src], at, b.W);
   }
 }
 
@@ -971,7 +1084,7 @@ int stack_supported(const PdrnnLstmDecodeStack& st) {
   return st.cell == 1 && pdrnn_gru_decode_supported(st.B, st.H, st.E, st.V, st.L, st.dtype);
 }
 
-template <class DT>
+template <class DT, int NT = 1>
 hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
   const PdrnnLstmDecodeStack& st = a->stack;
   LayerArgs k{};
@@ -979,9 +1092,21 @@ hipError_t decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream
   k.s.B = st.B;
   k.s.V = st.V;
   k.s.N = n_tokens;
-  PDRNN_HIP_CHECK((decode_positions<DT, Pick::beam>(st, n_tokens, k, stream)));
-  lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(k.b, n_tokens - 1, a->hyp, a->hyp_lp);
+  PDRNN_HIP_CHECK((decode_positions<DT, Pick::beam, NT>(st, n_tokens, k, stream)));
+  if constexpr (NT == 1) lstm_decode_beam_pick<<<1, kThreads, 0, stream>>>(k.b, n_tokens - 1, a->hyp, a->hyp_lp);
+  else lstm_decode_beam_pick_wide<<<1, kThreads, 0, stream>>>(k.b, n_tokens - 1, a->hyp, a->hyp_lp);
   return hipGetLastError();
+}
+
+// the wide search by its tile count NT = ceil(G W / 16)
+template <class DT>
+hipError_t decode_beam_wide(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
+  switch ((a->stack.B + kStreams - 1) / kStreams) {
+    case 2: return decode_beam<DT, 2>(a, n_tokens, stream);
+    case 3: return decode_beam<DT, 3>(a, n_tokens, stream);
+    case 4: return decode_beam<DT, 4>(a, n_tokens, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 template <class DT, int NT = 1>
@@ -1081,6 +1206,29 @@ hipError_t pdrnn_lstm_decode_beam(const PdrnnLstmDecodeBeamArgs* a, int n_tokens
     return hipErrorInvalidValue;
   return st.dtype == 0 ? pdrnn::decode_beam<pdrnn::BF16>(a, n_tokens, stream)
                        : pdrnn::decode_beam<pdrnn::F16>(a, n_tokens, stream);
+}
+
+// 17 to 64 streams of groups of up to 16 beams; every other limit is the wide decode predicate's
+int pdrnn_lstm_decode_beam_wide_supported(int G, int W, int H, int E, int V, int L, int dtype) {
+  return G >= 1 && W >= 1 && W <= pdrnn::kStreams && G <= pdrnn::kWideStreams && G * W <= pdrnn::kWideStreams &&
+         pdrnn_lstm_decode_wide_supported(G * W, H, E, V, L, dtype);
+}
+
+int pdrnn_gru_decode_beam_wide_supported(int G, int W, int H, int E, int V, int L, int dtype) {
+  return pdrnn_lstm_decode_beam_wide_supported(G, W, H, E, V, L, dtype) &&
+         pdrnn_gru_decode_wide_supported(G * W, H, E, V, L, dtype);
+}
+
+hipError_t pdrnn_lstm_decode_beam_wide(const PdrnnLstmDecodeBeamArgs* a, int n_tokens, hipStream_t stream) {
+  const PdrnnLstmDecodeStack& st = a->stack;
+  const bool fits = st.cell == 0   ? pdrnn_lstm_decode_beam_wide_supported(a->G, a->W, st.H, st.E, st.V, st.L, st.dtype)
+                    : st.cell == 1 ? pdrnn_gru_decode_beam_wide_supported(a->G, a->W, st.H, st.E, st.V, st.L, st.dtype)
+                                   : 0;
+  if (n_tokens < 1 || !fits || st.B != a->G * a->W) return hipErrorInvalidValue;
+  if (a->stop < -1 || a->stop >= st.V || (a->hyp_lp != nullptr && a->lp == nullptr) || a->hyp == nullptr)
+    return hipErrorInvalidValue;
+  return st.dtype == 0 ? pdrnn::decode_beam_wide<pdrnn::BF16>(a, n_tokens, stream)
+                       : pdrnn::decode_beam_wide<pdrnn::F16>(a, n_tokens, stream);
 }
 
 hipError_t pdrnn_lstm_decode_beam_select(const float* logits, float* cum, int32_t* done, int64_t* tokens,

@@ -248,7 +248,12 @@ class CharLM(nn.Module):
 
         Routing as in ``generate``: ``prompt[:, :-1]`` runs through ``forward``
         from ``state``; 16-bit models the decode kernels cover run on them,
-        ``16 // beam_width`` prompts per call; everything else takes the
+        ``64 // beam_width`` prompts per call on the wide-tile kernels wherever
+        that is more than 16 streams (every width measured faster there than in
+        chunks of 16 streams: profiles/r21/beam_wide.md), a remainder of 16
+        streams or fewer, and every call that fits 16, ``16 // beam_width``
+        prompts per call on the 16-stream kernels; a prompt's result does not
+        depend on the grouping, bit for bit.  Everything else takes the
         reference path, ``forward`` one token at a time -- an error under
         ``PDRNN_KERNELS=hip-strict``.  Dropout is off and the truncated-BPTT
         carry is left as it was."""
@@ -260,16 +265,21 @@ class CharLM(nn.Module):
         N, W = int(num_tokens), int(beam_width)
         with self._decoding("beam_search", prompt, state) as (_, first, state, cdt, plain):
             B = first.shape[0]
-            per = dec.MAX_STREAMS // W
+            per, per_wide = dec.MAX_STREAMS // W, dec.MAX_WIDE_STREAMS // W
             if plain and dec.beam_supported(min(B, per), W, H, E, V, L, cdt, dev, self.cell):
-                outs = []
-                for b0 in range(0, B, per):
-                    rows = slice(b0, min(b0 + per, B))
-                    o = dec.beam_decode(
+                wide = (min(B, per_wide) * W > dec.MAX_STREAMS
+                        and dec.beam_wide_supported(min(B, per_wide), W, H, E, V, L, cdt, dev, self.cell))
+                outs, b0 = [], 0
+                while b0 < B:
+                    # a chunk of more than 16 streams on the wide kernels, one of 16 or fewer on the 16-stream ones
+                    many = wide and min(B - b0, per_wide) * W > dec.MAX_STREAMS
+                    rows = slice(b0, min(b0 + (per_wide if many else per), B))
+                    o = (dec.beam_decode_wide if many else dec.beam_decode)(
                         self.embedding.weight, self.rnn._weights(), self.fc.weight, self.fc.bias, cdt,
                         *self._entering(state, rows), first[rows], N, W, stop=stop, return_logprobs=return_logprobs,
                         cell=self.cell)
                     outs.append(o[:3] + (self._leaving(o[3], o[4]),))
+                    b0 = rows.stop
             else:
                 _ext.fallback(f"char-LM beam search (B={B}, W={W}, H={H}, E={E}, V={V}, layers={L}, {cdt})", dev)
                 outs = [dec.beam_reference(self._step, state, first, N, W, stop=stop, return_logprobs=return_logprobs)]

@@ -40,8 +40,11 @@ both filters, and its log-probability is the argmax's at temperature 1.
 
 Beam search (``beam_select`` is the mirror of one position; ``beam_decode`` the
 fused op, ``beam_reference`` the host loop; decode_rng.h states the rule once).
-A launch holds G groups (prompts) of W beams, G * W <= 16; stream ``s = g * W +
-j`` is beam j of group g.
+A launch holds G groups (prompts) of W beams, G * W <= 16 (``beam_decode``) or
+17 to 64 (``beam_decode_wide``: the wide-tile kernels, a group free to lie
+across a tile of 16; a group's results and per-position record are bit for bit
+those of ``beam_decode`` on any call that holds it); stream ``s = g * W + j`` is
+beam j of group g.
 
     start   the W streams of a group enter position 0 with the prompt's state
             and last token; cum[0] = 0, cum[j > 0] = -inf, done = false
@@ -85,7 +88,8 @@ CELLS = ("lstm", "gru")
 
 __all__ = ["gumbel_noise", "keep_threshold", "token_logprobs", "check_filters", "sample", "supported", "alloc_buffers",
            "decode", "reference", "MAX_STREAMS", "MAX_WIDE_STREAMS", "CELLS", "check_beam", "beam_start", "beam_select", "beam_backtrace",
-           "stop_lengths", "beam_finish", "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference"]
+           "stop_lengths", "beam_finish", "beam_supported", "alloc_beam_buffers", "beam_decode", "beam_reference",
+           "beam_wide_supported", "beam_decode_wide"]
 
 MAX_STREAMS = 16  # streams of one MFMA tile (its 16-wide side): a beam search's limit
 MAX_WIDE_STREAMS = 64  # streams per launch of the wide-tile kernels: four tiles
@@ -349,13 +353,15 @@ def decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Op
     return out + ((bufs["threshold"],) if return_threshold else ()) + ((bufs["logprobs"],) if return_logprobs else ())
 
 
-def check_beam(width: int, stop: Optional[int], V: int, num_tokens: int = 1, groups: int = 1) -> None:
-    """ValueError unless 1 <= width <= 16, groups * width <= 16, stop is None
-    or a token of the vocabulary, and num_tokens >= 1."""
+def check_beam(width: int, stop: Optional[int], V: int, num_tokens: int = 1, groups: int = 1,
+               max_streams: int = MAX_STREAMS) -> None:
+    """ValueError unless 1 <= width <= 16, groups * width <= ``max_streams``
+    (16; the wide op's 64), stop is None or a token of the vocabulary, and
+    num_tokens >= 1."""
     if int(width) != width or not 1 <= width <= MAX_STREAMS:
         raise ValueError(f"beam_width must be an integer in [1, {MAX_STREAMS}], not {width}")
-    if groups < 1 or groups * width > MAX_STREAMS:
-        raise ValueError(f"{groups} groups of {width} beams do not fit a launch's {MAX_STREAMS} streams")
+    if groups < 1 or groups * width > max_streams:
+        raise ValueError(f"{groups} groups of {width} beams do not fit a launch's {max_streams} streams")
     if stop is not None and not 0 <= int(stop) < V:
         raise ValueError(f"stop token {stop} is outside the vocabulary")
     if int(num_tokens) < 1:
@@ -446,6 +452,12 @@ def beam_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.
     return _covered(_op(cell, "decode_beam"), dtype, device, G, W, H, E, V, L)
 
 
+def beam_wide_supported(G: int, W: int, H: int, E: int, V: int, L: int, dtype: torch.dtype, device,
+                        cell: str = "lstm") -> bool:
+    """The wide-tile decode kernels run a beam search of G groups of W beams, 17 <= G * W <= 64, on a ``cell`` stack."""
+    return _covered(_op(cell, "decode_beam_wide"), dtype, device, G, W, H, E, V, L)
+
+
 def alloc_beam_buffers(L: int, G: int, W: int, H: int, V: int, N: int, cdt: torch.dtype, device,
                        return_logits: bool = False, return_logprobs: bool = False) -> Dict[str, Optional[Tensor]]:
     """The buffers one ``beam_decode`` call works in, S = G * W: ``h``
@@ -480,12 +492,21 @@ def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_
     (hyp [G, W, N] int64 in rank order, scores [G, W] fp32, hyp_lp [G, W, N] or
     None, h [L, G * W, H] in ``cdt``, c [L, G * W, H] fp32): the state entering
     position N of each hypothesis, the last token not fed, as in ``decode``
-    (``cell="gru"``: c0 None, and the last result is h's fp32 master)."""
+    (``cell="gru"``: c0 None, and the last result is h's fp32 master).
+    More than 16 streams are ``beam_decode_wide``'s."""
+    return _beam_decode(False, emb_w, lstm_weights, fc_w, fc_b, cdt, h0, c0, first, num_tokens, width, stop,
+                        return_logits, return_logprobs, bufs, cell)
+
+
+def _beam_decode(wide: bool, emb_w, lstm_weights, fc_w, fc_b, cdt, h0, c0, first, num_tokens, width, stop,
+                 return_logits, return_logprobs, bufs, cell):
+    """``beam_decode`` (``wide``: ``beam_decode_wide``): the checks, the buffers and the one call."""
     dev, mod, V, E, H, L = _stack_dims(emb_w, lstm_weights, fc_w)
     G, N, W = first.shape[0], int(num_tokens), int(width)
-    check_beam(width, stop, V, N, G)
-    if mod is None or not beam_supported(G, W, H, E, V, L, cdt, dev, cell):
-        raise RuntimeError(f"{cell}_decode_beam does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
+    op = "decode_beam_wide" if wide else "decode_beam"
+    check_beam(width, stop, V, N, G, MAX_WIDE_STREAMS if wide else MAX_STREAMS)
+    if mod is None or not (beam_wide_supported if wide else beam_supported)(G, W, H, E, V, L, cdt, dev, cell):
+        raise RuntimeError(f"{cell}_{op} does not cover G={G} W={W} H={H} E={E} V={V} L={L} {cdt} on {dev}")
     with torch.no_grad():
         stack = _stack_operands(emb_w, lstm_weights, fc_w, fc_b, cdt, cell)
         if bufs is None:
@@ -494,7 +515,7 @@ def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_
         _init_state(cell, h, c, h0, c0, beams=W)
         bufs["cum"][0].copy_(beam_start(G, W, dev))
         bufs["done"][0].zero_()
-        getattr(mod, _op(cell, "decode_beam"))(
+        getattr(mod, _op(cell, op))(
             *stack, h, c, bufs["scratch"], first.to(dev, torch.int64).repeat_interleave(W).contiguous(),
             bufs["cum"], bufs["done"], bufs["tokens"], bufs["parents"],
             bufs["lp"] if return_logprobs else None, bufs["logits"] if return_logits else None,
@@ -503,6 +524,19 @@ def beam_decode(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_
         hn, cn = h[N & 1].index_select(1, last), c.index_select(1, last)
     return (bufs["hyp"].view(G, W, N), bufs["cum"][N].view(G, W),
             bufs["hyp_lp"].view(G, W, N) if return_logprobs else None, hn, cn)
+
+
+def beam_decode_wide(emb_w: Tensor, lstm_weights: Sequence[Tensor], fc_w: Tensor, fc_b: Optional[Tensor], cdt: torch.dtype,
+                     h0: Optional[Tensor], c0: Optional[Tensor], first: Tensor, num_tokens: int, width: int, *,
+                     stop: Optional[int] = None, return_logits: bool = False, return_logprobs: bool = False,
+                     bufs: Optional[Dict[str, Optional[Tensor]]] = None, cell: str = "lstm"):
+    """``beam_decode`` for 17 <= G * width <= 64 streams on the wide-tile
+    kernels: the same arguments, buffers, launches and returns.  A group's
+    hypotheses, scores, log-probs, state and per-position record (parents
+    relative to the group's first stream) are bit for bit ``beam_decode``'s on
+    any call that holds the group."""
+    return _beam_decode(True, emb_w, lstm_weights, fc_w, fc_b, cdt, h0, c0, first, num_tokens, width, stop,
+                        return_logits, return_logprobs, bufs, cell)
 
 
 def beam_reference(step: Callable[[Tensor, object], Tuple[Tensor, object]], state, first: Tensor, num_tokens: int,
